@@ -15,6 +15,10 @@ textures) and asserts that every step encoded its clip (``clips_encoded == steps
 (``SamPt.forward_begin`` / ``forward_end``: the decoder chain of clip i overlaps the tracker encoder of clip i + 1; exactly
 ``--steps`` clips are submitted AND collected between the two barriers); ``--submit pipelined`` makes that the ``value``.
 
+A plain run times the headline loop only.  ``--full`` adds everything else the line can carry: the second loop
+(``value_pipelined``), the forward timeline, the GEMM roofline, the secondary lines, the f16x3 side line and the CPU oracle
+leg (``cpu_baseline`` + ``parity``).  ``--dump-outputs DIR`` writes what the last timed step returned (``dump_outputs``).
+
 Launch: ``python bench.py --gpus 1`` or ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N``.
 """
 import argparse
@@ -29,6 +33,8 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
+
+DUMP_SAMPLE = 1 << 22     # --dump-outputs: 16 MB of float32 per array at most, two large arrays (masks, logits) -> < 64 MB
 
 
 def parse():
@@ -109,6 +115,14 @@ def parse():
     ap.add_argument("--shard-fnet", action="store_true",
                     help="--shard frames: also shard the tracker's per-frame encoder and all_gather its feature pyramid (an extra "
                          "collective north_star does not have; default off: the uint8 mask gather is the only collective)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the second timed loop (value_pipelined / value_per_forward), the "
+                         "forward timeline, the GEMM roofline, the secondary lines, the f16x3 side line and the CPU oracle leg "
+                         "(cpu_baseline + parity), each still subject to its --no-* switch.  Without it a run sets up, warms up, "
+                         "times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; an array of "
+                         "more than %d elements as that many elements at fixed seeded positions)" % DUMP_SAMPLE)
     return ap.parse_args()
 
 
@@ -154,11 +168,13 @@ def consume(model, out, max_frames):
 
 
 def one_step(model, video, max_frames, shard="sequences", shard_fnet=False):
+    """-> (index masks, gathered masks, SamPt.forward result or None when the clip is frame-sharded)"""
     from sam_pt_amd.dist import sharded_forward
     if shard == "frames":
         full, _ = sharded_forward(model, video, batch=8, shard_fnet=shard_fnet)   # rank 0: the (T,H,W) index masks; others: None
-        return full, full
-    return consume(model, model(video), max_frames)
+        return full, full, None
+    out = model(video)
+    return consume(model, out, max_frames) + (out,)
 
 
 class ClipsInFlight:
@@ -166,7 +182,7 @@ class ClipsInFlight:
     (forward_end + consume); ``flush`` collects the last.  K submits + one flush = K clips submitted and collected."""
 
     def __init__(self, model, max_frames):
-        self.model, self.max_frames, self.pending, self.last = model, max_frames, None, None
+        self.model, self.max_frames, self.pending, self.last, self.last_out = model, max_frames, None, None, None
 
     def submit(self, video):
         h = self.model.forward_begin(video)
@@ -176,9 +192,31 @@ class ClipsInFlight:
 
     def flush(self):
         if self.pending is not None:
-            out, self.pending = self.model.forward_end(self.pending), None
-            self.last = consume(self.model, out, self.max_frames)[0]
+            self.last_out, self.pending = self.model.forward_end(self.pending), None
+            self.last = consume(self.model, self.last_out, self.max_frames)[0]
         return self.last
+
+
+def dump_outputs(path, masks, out):
+    """``--dump-outputs``: what the last timed step handed its caller, as float32 ``.npy`` files — the index masks of
+    ``consume`` and the ``SamPt.forward`` result (logits stacked to (M, T, H, W), trajectories, visibilities, scores).  An
+    array of more than DUMP_SAMPLE elements is written flattened, as the elements at DUMP_SAMPLE sorted positions drawn by a
+    generator seeded with 0: the same shape gives the same positions, so two builds compare element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"masks": masks}
+    if out is not None:
+        arrays.update(logits=torch.stack([torch.as_tensor(l) for l in out["logits"]]), trajectories=out["trajectories"],
+                      visibilities=out["visibilities"], scores=torch.tensor(out["scores"]),
+                      scores_per_frame=torch.tensor(out["scores_per_frame"]))
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        a = torch.as_tensor(a).detach()
+        if a.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            a = a.reshape(-1)[idx.to(a.device)]
+        np.save(os.path.join(path, name + ".npy"), a.float().cpu().numpy())
 
 
 def gemm_roofline(args, dev, insitu=None, frame_hw=(576, 1024)):
@@ -719,10 +757,13 @@ def main():
         def step(i):
             v0 = clips[i % 2]
             vs = [v0] if not lpt else [{**v0, "image": v0["image"][:L]} for L in mine]   # this rank's sequences
-            m = None
+            m = out = None
             for v in vs:                                    # one SamPt.forward each (+ mask gather)
-                m = flight.submit(v) if pipelined else one_step(model, v, args.frames, shard, args.shard_fnet)[0]
-            return m
+                if pipelined:
+                    m, out = flight.submit(v), flight.last_out
+                else:
+                    m, _, out = one_step(model, v, args.frames, shard, args.shard_fnet)
+            return m, out
         return step
 
     if lpt and world > 1:                               # ranks hold different numbers of sequences: gather per step instead
@@ -730,18 +771,19 @@ def main():
 
         def make_step(pipelined):                       # noqa: F811  (masks stay local; one gather of the last one per step)
             def step(i):
-                m = None
+                m = out = None
                 for L in mine:
                     out = model({**clips[i % 2], "image": clips[i % 2]["image"][:L]})
                     m = index_masks(torch.stack(out["logits"], dim=0))
                 if m is None:
                     m = torch.zeros((0, H, W), dtype=torch.uint8, device=dev)
                 gather_masks(m, args.frames)
-                return m
+                return m, out
             return step
 
     def timed_loop(pipelined):
-        """W warm-up steps, then EXACTLY K steps between two barriers; max over ranks.  -> (seconds, last masks, frames encoded)"""
+        """W warm-up steps, then EXACTLY K steps between two barriers; max over ranks.
+        -> (seconds, last masks, frames encoded, last SamPt.forward result)"""
         step = make_step(pipelined)
         for i in range(args.warmup):
             step(i)
@@ -751,19 +793,22 @@ def main():
         n0 = enc_stats["encoded_frames"]
         t0 = time.perf_counter()
         for i in range(args.steps):
-            m = step(i)
+            m, out = step(i)
         if pipelined:
-            m = flight.flush()                          # the last clip is collected INSIDE the timed region
+            m, out = flight.flush(), flight.last_out    # the last clip is collected INSIDE the timed region
         barrier()
         dt = time.perf_counter() - t0
         if world > 1:
             tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dt = float(tmax.item())
-        return dt, m, enc_stats["encoded_frames"] - n0
+        return dt, m, enc_stats["encoded_frames"] - n0, out
 
     value_pipelined_first = args.submit == "pipelined" and can_pipeline
-    dt, masks, n_enc = timed_loop(value_pipelined_first)
+    dt, masks, n_enc, out_last = timed_loop(value_pipelined_first)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, masks, out_last)
+    del out_last
     total_frames = (lpt_info["frames_total"] if lpt else (1 if frames_sharded else world) * args.frames) * args.steps
     fps = total_frames / dt
     # every timed step ran the image encoder over its own clip (nothing is keyed on a clip and reused): frames this rank encoded
@@ -780,8 +825,8 @@ def main():
     # The same K steps once more the OTHER way (pipelined after blocking, or blocking after pipelined); same barriers, same max
     # over ranks, same alternating clips.
     fps_other = dt_other = None
-    if can_pipeline and not args.no_pipelined:
-        dt_other, _, n_enc2 = timed_loop(not value_pipelined_first)
+    if args.full and can_pipeline and not args.no_pipelined:
+        dt_other, _, n_enc2, _ = timed_loop(not value_pipelined_first)
         assert n_enc2 == frames_expected, (n_enc2, frames_expected)
         fps_other = total_frames / dt_other
     if value_pipelined_first:
@@ -790,7 +835,8 @@ def main():
         fps_pipe, dt_pipe, fps_seq, dt_seq = fps_other, dt_other, fps, dt
     pipelined = value_pipelined_first
     insitu = None
-    if rank == 0 and not args.no_roofline and args.precision in ("f16", "f16x3"):   # one more step, GEMM launches event-timed
+    if rank == 0 and args.full and not args.no_roofline and args.precision in ("f16", "f16x3"):
+        # one more step, GEMM launches event-timed
         model.sam_predictor.gemm_profile_begin()
         one_step(model, video, args.frames) if world == 1 else model(video)
         torch.cuda.synchronize()
@@ -843,32 +889,33 @@ def main():
         if lpt_info:
             res["lpt"] = lpt_info
         if world == 1 and not frames_sharded and not lpt:
-            # where one blocking forward spends its wall time (GPU-side event times, ms after the start of the forward): tracker
-            # encoder done, window chain done, image encoder done, decoder chain done (tools/forward_timeline.py)
-            tl_ms = {}
-            for _ in range(2):
-                model.timeline = {}
-                one_step(model, video, args.frames)
-                torch.cuda.synchronize()
-                e0 = model.timeline["start"][0]
-                tl_ms = {k: round(e0.elapsed_time(ev), 1) for k, (ev, _) in model.timeline.items() if k != "start"}
-            model.timeline = None
-            res["timeline"] = {"unit": "ms after the forward's first launch (GPU events), one blocking forward", **tl_ms}
+            if args.full:
+                # where one blocking forward spends its wall time (GPU-side event times, ms after the start of the forward):
+                # tracker encoder done, window chain done, image encoder done, decoder chain done (tools/forward_timeline.py)
+                tl_ms = {}
+                for _ in range(2):
+                    model.timeline = {}
+                    one_step(model, video, args.frames)
+                    torch.cuda.synchronize()
+                    e0 = model.timeline["start"][0]
+                    tl_ms = {k: round(e0.elapsed_time(ev), 1) for k, (ev, _) in model.timeline.items() if k != "start"}
+                model.timeline = None
+                res["timeline"] = {"unit": "ms after the forward's first launch (GPU events), one blocking forward", **tl_ms}
             lpr = getattr(model.point_tracker, "stats", {}).get("launches_per_round")
             if lpr:
                 res["chain_launches_per_round"] = lpr
-        if not args.no_roofline and args.precision in ("f16", "f16x3"):
+        if args.full and not args.no_roofline and args.precision in ("f16", "f16x3"):
             res["roofline"] = gemm_roofline(args, dev, insitu, (H, W))
             if args.precision == "f16":
                 res["roofline"]["secondary"] = secondary_rooflines(args, dev)
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             res["secondary"] = secondary_lines(args, model, video, dev)
             if headline and args.precision == "f16" and not args.no_roofline:
                 # the reference-grade arithmetic (split-fp16: the reference's fp32 ViT at fp32 grade) as a FULL line of its own —
                 # the same K timed steps, its own in-situ roofline block — from a child process running this very script
                 import subprocess
                 cmd = [sys.executable, os.path.abspath(__file__), "--precision", "f16x3", "--steps", str(args.steps), "--warmup",
-                       str(args.warmup), "--no-cpu-baseline", "--no-secondary", "--no-pipelined"]
+                       str(args.warmup), "--full", "--no-cpu-baseline", "--no-secondary", "--no-pipelined"]
                 try:
                     pr = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
                     line = [l for l in pr.stdout.splitlines() if l.startswith("{")]
@@ -879,13 +926,13 @@ def main():
             res["frame_sharding_model"] = frame_sharding_model(args, model, video)
         if world == 1 and args.lpt_model:
             res["sequence_sharding_model"] = sequence_sharding_model(args, model, dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the timed configuration's result, compared with the oracle: with pipelined submission the clip that had the
             # next one submitted on top of it (its decoder chain ran beside that one's tracker encoder)
             out = list(model.stream([video, video]))[0] if pipelined else model(video)
             torch.cuda.synchronize()
             res["cpu_baseline"], res["parity"] = cpu_reference(args, frames, qp, out)
-        elif world == 1:
+        elif args.full and world == 1:
             out = list(model.stream([video, video]))[0] if pipelined else model(video)
             torch.cuda.synchronize()
             par = cached_parity(args, frames, qp, out)

@@ -12,6 +12,8 @@ reference's own code run in place from /root/reference (never copied):
   sampt_patch.npz   SamPt.forward with use_patch_matching_filtering (rgb2lab substituted by our restatement)
   pips2.npz         sam_pt.point_tracker.pips_plus_plus.{PipsPlusPlus, PipsPlusPlusPointTracker}   (row f4)
   sam_hq_hf.npz     HuggingFace transformers SamHQModel                   (secondary pin of the absent HQ-SAM decoder)
+  reference_pins.npz  Pips / PipsPlusPlus state-dict layouts, one Pips window, random / mixed point selection and
+                    oracle.parity.reference_run driven by the reference SamPt class
 
 Weights are NOT stored: they are regenerated from the seed (sam_pt_amd/weights.py), inputs from
 sam_pt_amd/synth.py.  Usage:  PYTHONDONTWRITEBYTECODE=1 python oracle/make_golden.py
@@ -169,6 +171,63 @@ def make_pips2_golden():
     np.savez_compressed(os.path.join(OUT, "pips2.npz"), **out)
 
 
+def _layout(module):
+    """State-dict layout as 'name:d0,d1,...' strings (what load_state_dict(strict=True) checks)."""
+    return np.array([f"{k}:{','.join(map(str, v.shape))}" for k, v in module.state_dict().items()])
+
+
+def make_reference_pins_golden():
+    """reference_pins.npz: what tests/test_oracle_pins.py once compared with the reference live — the state-dict layouts of the
+    reference Pips and PipsPlusPlus, one window of the reference Pips on frames 2-9, the reference's random / mixed point
+    selection under fixed seeds, and reference_run driven by the reference SamPt class.  The IoU-threshold case's logits are
+    stored as mask bits plus a rejected (-inf) flag per (object, frame), the embeddings as one stripe per frame."""
+    import importlib
+    from oracle.parity import reference_run
+    from sam_pt_amd.weights import init_pips2_state_dict
+    out = {}
+    Pips, _, _ = RL.load_pips()
+    Pips2, _ = RL.load_pips2()
+    psd = init_pips_state_dict(72)
+    out["pips_layout"] = _layout(Pips(S=8, stride=4))
+    out["pips2_layout"] = _layout(Pips2(stride=8))
+    frames, centres = synthetic_clip(T=12, H=128, W=256, seed=72)
+    m = Pips(S=8, stride=4).eval()
+    m.load_state_dict(psd, strict=True)
+    q = disc_queries(centres, n_pos=3, r=7.0)
+    with torch.no_grad():
+        preds, _, vis, ffeat, _ = m(q[None, :, 1:], frames[None, 2:10].float(), iters=6, return_feat=True)
+    out["live_traj"], out["live_vis"], out["live_ffeat"] = preds[-1][0].numpy(), vis[0].numpy(), ffeat[0].numpy()
+    RL.load_sam_pt()
+    ref = importlib.import_module("sam_pt.utils.query_points")
+    mk = (torch.rand(40, 60, generator=torch.Generator().manual_seed(1)) > 0.7).float()
+    for n in (3, 8, 5000):
+        torch.manual_seed(9)
+        out[f"random_{n}"] = ref.extract_random_mask_points(mk, n).numpy()
+    masks, ts, imgs = [mk, 1 - mk], torch.tensor([0.0, 1.0]), torch.zeros(2, 3, 40, 60, dtype=torch.uint8)
+    for n in (1, 2):
+        torch.manual_seed(4)
+        parts = ref.extract_mixed_points(masks, ts, imgs, n)
+        for i, p in enumerate(parts):
+            out[f"mixed_{n}_{i}"] = p.numpy()
+    cfg = SAM_CONFIGS["vit_test"]
+    sd = init_sam_state_dict(cfg, 72)
+    frames, centres = synthetic_clip(T=9, H=128, W=256, seed=72)
+    q = disc_queries(centres, n_pos=5, r=9.0)
+    q2 = disc_queries(centres, n_pos=5, r=5.0)
+    q2[:, 1:] += torch.tensor([-60.0, 20.0])
+    kw = dict(sam_iou_threshold=0.06, positive_points_per_mask=4, negative_points_per_mask=1, iterative_refinement_iterations=3,
+              point_tracker_mask_batch_size=5)
+    a = reference_run(cfg, sd, psd, frames, torch.stack([q, q2]), kw, frame_ids=[0, 3, 8], use_reference=True)
+    logits = torch.stack([torch.as_tensor(x) for x in a["logits"]])
+    out["drivers_traj"], out["drivers_vis"] = a["trajectories"].numpy(), a["visibilities"].numpy()
+    out["drivers_masks"] = np.packbits((logits > 0).numpy(), axis=-1)
+    out["drivers_rejected"] = torch.isneginf(logits).all(-1).all(-1).numpy()
+    out["drivers_scores_per_frame"] = torch.as_tensor(a["scores_per_frame"], dtype=torch.float32).numpy()
+    out["drivers_predict_calls"] = np.array(a["seconds"]["predict_calls"])
+    out["drivers_emb_stripe"] = torch.as_tensor(a["embeddings"])[..., 5, :].numpy()
+    np.savez_compressed(os.path.join(OUT, "reference_pins.npz"), **out)
+
+
 def main():
     assert RL.available(), "the reference tree is required to (re)generate goldens"
     os.makedirs(OUT, exist_ok=True)
@@ -252,6 +311,7 @@ def main():
     make_hq_golden()
     make_pips2_golden()
     make_patch_golden()
+    make_reference_pins_golden()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)) // 1024, "KiB")
 

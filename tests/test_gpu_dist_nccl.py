@@ -89,7 +89,7 @@ def test_bench_under_torch_distributed_run():
     """bench.py launched as the driver launches it for N > 1 (rendezvous from the environment), one rank: one JSON line with the
     contract's fields, `clips_encoded == steps`."""
     r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--model", "vit_b", "--frames", "8",
-                   "--no-cpu-baseline", "--no-secondary", "--no-roofline"])
+                   "--full", "--no-cpu-baseline", "--no-secondary", "--no-roofline"])
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
