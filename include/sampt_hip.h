@@ -336,6 +336,30 @@ int sampt_sam_decode_multimask(sampt_dec_t h, const float* features_dev, const f
                                int k, const float* box_dev, const float* mask_in_dev, int in_h, int in_w, int out_h,
                                int out_w, float* logits_out_dev, float* iou_out_dev, float* low_res_out_dev,
                                void* workspace_dev, size_t workspace_bytes, sampt_stream_t stream);
+/* n point prompts against ONE image in one batched launch sequence (the automatic mask generator's inner step).
+ * features_dev [grid*grid][256] of that image (not n copies), hq_features_dev [16*grid*grid][32] (HQ-SAM handles) or NULL;
+ * pts_dev [n][k][2] (input-frame pixels), labels_dev int32 [n][k], k >= 1; no box, no mask input.  n <= max_frames of the handle.
+ * Outputs: low_res_out_dev [n][m][4*grid][4*grid], iou_out_dev [n][m]; nothing at full resolution (see the amg functions below).
+ * m = 3 for a SAM handle with multimask != 0 (mask tokens 1..3 in that order, as the multimask entry point above), m = 1
+ * otherwise.  HQ-SAM with multimask != 0 follows MaskDecoderHQ.forward with hq_token_only=False: of mask tokens 1..3 the one with
+ * the largest predicted IoU is chosen ON THE DEVICE, the output is its SAM mask + the HQ mask and that IoU.  Image-side work
+ * that does not depend on the prompt (features + no_mask_embed, the layer-0 K | V | Q' projection) runs once per call. */
+int sampt_sam_decode_points_workspace_bytes(sampt_dec_t h, int n, int k, size_t* bytes);
+int sampt_sam_decode_points(sampt_dec_t h, int n, const float* features_dev, const float* hq_features_dev, const float* pts_dev,
+                            const int32_t* labels_dev, int k, int multimask, float* low_res_out_dev, float* iou_out_dev,
+                            void* workspace_dev, size_t workspace_bytes, sampt_stream_t stream);
+/* Scoring tail of the automatic mask generator on low-res masks low_res_dev [n_masks][L][L].  With v = Sam.postprocess_masks of a
+ * mask, evaluated on the fly with the arithmetic of the postprocess entry point below (no logits are written):
+ * score: out8_dev int32 [n_masks][8] = { #(v > thr + offset), #(v > thr - offset), #(v > thr), x0, y0, x1, y1, 0 } with the
+ *   inclusive XYXY box of v > thr (zeros for an empty mask); thresholds are formed in double and rounded to float once, as a
+ *   float tensor compared with a Python scalar.  Integer partial sums + a final reducer: bitwise reproducible.
+ * binarize: out_dev bytes [n_rows][out_h][out_w] = (v(low_res[rows_dev[r]]) > thr) as 0 / 1, any out_h x out_w. */
+size_t sampt_amg_score_workspace_bytes(int n_masks);
+int sampt_amg_score(const float* low_res_dev, int n_masks, int L, int img_size, int in_h, int in_w, int out_h, int out_w,
+                    double mask_threshold, double offset, int32_t* out8_dev, void* workspace_dev, size_t workspace_bytes,
+                    sampt_stream_t stream);
+int sampt_amg_binarize(const float* low_res_dev, int n_masks, const int32_t* rows_dev, int n_rows, int L, int img_size, int in_h,
+                       int in_w, int out_h, int out_w, double mask_threshold, uint8_t* out_dev, sampt_stream_t stream);
 /* Whole SamPt.predict_mask chain (sam_pt.py:760-837) for `frames` independent (frame, object) items that share the
  * visible-point count k, batched into one launch sequence and without host synchronisation:
  * [positives-only pass over the first n_pos_first points when n_pos_first >= 0, i.e. negative_points_per_mask > 0;

@@ -74,6 +74,11 @@ _SIGS = {
     "sampt_sam_decode": (c_int, [_P, _P, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t,
                                  _P]),
     "sampt_sam_decode_multimask": (c_int, [_P, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "sampt_sam_decode_points_workspace_bytes": (c_int, [_P, c_int, c_int, C.POINTER(c_size_t)]),
+    "sampt_sam_decode_points": (c_int, [_P, c_int, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "sampt_amg_score_workspace_bytes": (c_size_t, [c_int]),
+    "sampt_amg_score": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, C.c_double, C.c_double, _P, _P, c_size_t, _P]),
+    "sampt_amg_binarize": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, C.c_double, _P, _P]),
     "sampt_sam_track_decode": (c_int, [_P, c_int, _P, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_float, c_int, c_int, c_int,
                                        c_int, _P, _P, _P, c_size_t, _P]),
     "sampt_sam_track_decode_graph": (c_int, [_P, c_int, _P, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_float, c_int, c_int,

@@ -15,8 +15,19 @@ constructor keywords and record format:
 
 MI355X notes: upstream run-length encodes every surviving mask on the host to bound memory; with 288 GB of HBM the boolean
 masks simply stay on the device until the records are built (RLE helpers are kept for ``output_mode="uncompressed_rle"``).
-All mask arithmetic is device tensor work on the predictor's device; the decoder passes go through the C ABI
-(``sampt_sam_decode_multimask``).  Parity: the helpers are pinned against transformers' independent port of the same
+Two paths through a batch of points, chosen by ``fused``:
+
+  * fused (default with the HIP ``SamPredictor``): ``predict_points_batch`` decodes the whole batch as ONE decoder chain against
+    the image (``sampt_sam_decode_points``: prompt-independent image work once per batch, all masks of a prompt from one pass
+    over its upscaled map, low-res masks only) -> ``score_masks`` (``sampt_amg_score``: the stability counts, the area and the
+    box of every candidate from its low-res mask, the full-resolution logits evaluated on the fly with the post-processing
+    kernel's own arithmetic and never written) -> the same three filters on the per-mask numbers -> ``binarize_masks``
+    (``sampt_amg_binarize``) for the survivors only.  Same survivors in the same order as the other path; with HQ-SAM one
+    candidate per point (MaskDecoderHQ's multimask rule).
+  * ``fused=False`` (and any predictor without ``predict_points_batch``, e.g. the CPU oracle): ``predict_torch`` prompt by
+    prompt (``sampt_sam_decode_multimask``) and device tensor work on the full-resolution logits.
+
+Parity: the helpers are pinned against transformers' independent port of the same
 utilities (tests/test_oracle_pins.py); box NMS restates torchvision's ``batched_nms`` (absent) and the small-region
 clean-up uses ``scipy.ndimage.label`` where upstream uses OpenCV (absent): **those two are parity-unpinned**.
 """
@@ -231,14 +242,16 @@ class _MaskData:
 
 class SamAutomaticMaskGenerator:
     """Constructor keywords of configs/vis_eval_root.yaml:13-28 (= upstream's).  ``predictor`` (tests) injects any object
-    with the ``SamPredictor`` interface instead of building one from ``model``."""
+    with the ``SamPredictor`` interface instead of building one from ``model``.  ``fused``: None = the batched decode + fused
+    scoring path when the predictor offers it (``predict_points_batch`` / ``score_masks`` / ``binarize_masks``), False = always
+    ``predict_torch`` and tensor work on full-resolution logits, True = insist on the fused path."""
 
     def __init__(self, model, points_per_side: Optional[int] = 32, points_per_batch: int = 64,
                  pred_iou_thresh: float = 0.88, stability_score_thresh: float = 0.95, stability_score_offset: float = 1.0,
                  box_nms_thresh: float = 0.7, crop_n_layers: int = 0, crop_nms_thresh: float = 0.7,
                  crop_overlap_ratio: float = 512 / 1500, crop_n_points_downscale_factor: int = 1,
                  point_grids: Optional[List[np.ndarray]] = None, min_mask_region_area: int = 0,
-                 output_mode: str = "binary_mask", predictor=None) -> None:
+                 output_mode: str = "binary_mask", predictor=None, fused: Optional[bool] = None) -> None:
         if (points_per_side is None) == (point_grids is None):
             raise ValueError("Exactly one of points_per_side or point_grids must be provided.")
         if points_per_side is not None:
@@ -258,6 +271,11 @@ class SamAutomaticMaskGenerator:
             from .sam_predictor import SamPredictor
             predictor = SamPredictor(model)
         self.predictor = predictor
+        can_fuse = all(hasattr(predictor, a) for a in ("predict_points_batch", "score_masks", "binarize_masks"))
+        if fused and not can_fuse:
+            raise ValueError(f"fused=True needs a predictor with predict_points_batch / score_masks / binarize_masks; "
+                             f"{type(predictor).__name__} has none (use fused=None or False)")
+        self.fused = can_fuse if fused is None else bool(fused)
         self.points_per_batch = points_per_batch
         self.pred_iou_thresh = pred_iou_thresh
         self.stability_score_thresh = stability_score_thresh
@@ -329,8 +347,9 @@ class SamAutomaticMaskGenerator:
         points = self.point_grids[layer] * np.array(crop_hw)[None, ::-1]          # (x, y) in crop pixels
         data = self._empty(*orig_size)
         del data.cols["crop_boxes"]
+        process = self._process_batch_fused if self.fused else self._process_batch
         for i in range(0, len(points), self.points_per_batch):
-            data.cat(self._process_batch(points[i:i + self.points_per_batch], crop_hw, crop_box, orig_size))
+            data.cat(process(points[i:i + self.points_per_batch], crop_hw, crop_box, orig_size))
         self.predictor.reset_image()
         data.filter(nms(data["boxes"].float(), data["iou_preds"], self.box_nms_thresh))
         data["boxes"] = uncrop_boxes_xyxy(data["boxes"], crop_box)
@@ -364,6 +383,35 @@ class SamAutomaticMaskGenerator:
             data.filter(keep)
         data["masks"] = uncrop_masks(data["masks"], crop_box, orig_h, orig_w)
         return data
+
+    def _process_batch_fused(self, points: np.ndarray, crop_hw: Tuple[int, int], crop_box: List[int],
+                             orig_size: Tuple[int, int]) -> _MaskData:
+        """``_process_batch`` without full-resolution logits: the filters run on the per-mask record of ``score_masks`` with the
+        same expressions in the same order, only the survivors are binarised."""
+        orig_h, orig_w = orig_size
+        dev = self._device
+        in_points = torch.as_tensor(self.predictor.transform.apply_coords(points, crop_hw), device=dev)
+        in_labels = torch.ones(in_points.shape[0], dtype=torch.int, device=dev)
+        low, iou_preds = self.predictor.predict_points_batch(in_points[:, None, :].float(), in_labels[:, None],
+                                                             multimask_output=True)
+        n_per_point = low.shape[1]
+        low = low.flatten(0, 1)
+        rec = self.predictor.score_masks(low, self.stability_score_offset)      # (N, 8) int32: hi, lo, area, x0, y0, x1, y1, 0
+        data = _MaskData(rows=torch.arange(low.shape[0], device=low.device), iou_preds=iou_preds.flatten(0, 1),
+                         points=torch.as_tensor(points.repeat(n_per_point, axis=0), device=low.device), rec=rec)
+        if self.pred_iou_thresh > 0.0:
+            data.filter(data["iou_preds"] > self.pred_iou_thresh)
+        data["stability_score"] = data["rec"][:, 0] / data["rec"][:, 1]
+        if self.stability_score_thresh > 0.0:
+            data.filter(data["stability_score"] >= self.stability_score_thresh)
+        data["boxes"] = data["rec"][:, 3:7].to(torch.int64)
+        keep = ~is_box_near_crop_edge(data["boxes"], crop_box, [0, 0, orig_w, orig_h])
+        if not bool(keep.all()):
+            data.filter(keep)
+        masks = self.predictor.binarize_masks(low, data["rows"])
+        out = _MaskData(masks=uncrop_masks(masks, crop_box, orig_h, orig_w), iou_preds=data["iou_preds"], points=data["points"],
+                        stability_score=data["stability_score"], boxes=data["boxes"])
+        return out
 
     @staticmethod
     def _postprocess_small_regions(data: _MaskData, min_area: int, nms_thresh: float) -> _MaskData:

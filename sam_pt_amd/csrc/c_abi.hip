@@ -549,6 +549,49 @@ int sampt_sam_decode_multimask(sampt_dec_t h, const float* features, const float
   return rc;
 }
 
+int sampt_sam_decode_points_workspace_bytes(sampt_dec_t h, int n, int k, size_t* bytes) {
+  if (!h || !bytes) return fail(SAMPT_ERR_ARG, "sampt_sam_decode_points_workspace_bytes: null handle / output");
+  if (n <= 0 || n > h->e.max_frames)
+    return fail(SAMPT_ERR_ARG, "sampt_sam_decode_points_workspace_bytes: n " + std::to_string(n) + " outside 1.." +
+                                   std::to_string(h->e.max_frames) + " (max_frames of sampt_dec_create)");
+  if (k <= 0 || k > SAMPT_DEC_MAX_POINTS)
+    return fail(SAMPT_ERR_ARG, "sampt_sam_decode_points_workspace_bytes: k = " + std::to_string(k) + " prompt points outside 1.." +
+                                   std::to_string(SAMPT_DEC_MAX_POINTS) + " (SAMPT_DEC_MAX_POINTS)");
+  Arena a(nullptr, 0);
+  float dummy = 0.f;
+  int rc = h->e.decode_points(n, &dummy, h->e.is_hq() ? &dummy : nullptr, &dummy, nullptr, k, true, nullptr, nullptr, a, nullptr);
+  *bytes = a.peak + 256;
+  return rc;
+}
+
+int sampt_sam_decode_points(sampt_dec_t h, int n, const float* features, const float* hq_features, const float* pts,
+                            const int32_t* labels, int k, int multimask, float* low_out, float* iou_out, void* ws, size_t ws_bytes,
+                            sampt_stream_t stream) {
+  if (!h || !features || !pts || !labels || !low_out || !iou_out || !ws || k <= 0 || k > SAMPT_DEC_MAX_POINTS)
+    return fail(SAMPT_ERR_ARG, "sampt_sam_decode_points: bad arguments");
+  if (n <= 0 || n > h->e.max_frames)
+    return fail(SAMPT_ERR_ARG, "sampt_sam_decode_points: n " + std::to_string(n) + " outside 1.." + std::to_string(h->e.max_frames) +
+                                   " (max_frames of sampt_dec_create)");
+  if (h->e.is_hq() != (hq_features != nullptr))
+    return fail(SAMPT_ERR_ARG, "sampt_sam_decode_points: hq_features must be given for HQ-SAM handles and only for them");
+  Arena a(ws, ws_bytes);
+  return h->e.decode_points(n, features, hq_features, pts, labels, k, multimask != 0, low_out, iou_out, a, (hipStream_t)stream);
+}
+
+size_t sampt_amg_score_workspace_bytes(int n_masks) { return amg_score_workspace_bytes(n_masks); }
+
+int sampt_amg_score(const float* low, int n_masks, int L, int img, int in_h, int in_w, int oh, int ow, double mask_threshold,
+                    double offset, int32_t* out8, void* ws, size_t ws_bytes, sampt_stream_t stream) {
+  int rc = amg_score(low, n_masks, L, img, in_h, in_w, oh, ow, mask_threshold, offset, (int*)out8, ws, ws_bytes, (hipStream_t)stream);
+  return rc == SAMPT_OK ? rc : fail(rc, "sampt_amg_score: bad arguments or workspace too small");
+}
+
+int sampt_amg_binarize(const float* low, int n_masks, const int32_t* rows, int n_rows, int L, int img, int in_h, int in_w, int oh,
+                       int ow, double mask_threshold, uint8_t* out, sampt_stream_t stream) {
+  int rc = amg_binarize(low, n_masks, (const int*)rows, n_rows, L, img, in_h, in_w, oh, ow, mask_threshold, out, (hipStream_t)stream);
+  return rc == SAMPT_OK ? rc : fail(rc, "sampt_amg_binarize: bad arguments");
+}
+
 int sampt_sam_track_decode(sampt_dec_t h, int frames, const float* features, const float* hq_features,
                            const float* pts, const int32_t* labels, int k, const int32_t* k_item,
                            const int32_t* npos_item, int ld_pts, int n_pos_first, int refine_iters, float iou_thr,

@@ -269,6 +269,11 @@ struct DecEngine {
   int track_decode(int F, const float* features, const float* hq_feat, const float* pts, const int* labels, int k,
                    const int* k_item, const int* npos_item, int ld_pts, int n_pos_first, int R, float iou_thr, int in_h, int in_w, int oh, int ow, float* final_logits, float* score_out,
                    Arena& ws, hipStream_t s);
+  // n single-image point prompts (pts [n][k][2], labels [n][k], k >= 1) against ONE image: features [g*g][C], hq_feat
+  // [16*g*g][C/8] or null.  low_out [n][m][4g][4g], iou_out [n][m]; m = 3 for SAM with multi, else 1 (HQ-SAM with multi: the
+  // SAM mask of the best-IoU token + the HQ mask).  Image-side work that does not depend on the prompt runs once per call.
+  int decode_points(int n, const float* features, const float* hq_feat, const float* pts, const int* labels, int k, bool multi,
+                    float* low_out, float* iou_out, Arena& ws, hipStream_t s);
 };
 
 }  // namespace sampt

@@ -8,6 +8,8 @@
 //   * the refinement box comes from an on-device bbox reduction and the reference's `m.sum() < 2 -> break` is a
 //     per-frame device-side predicate (later passes still run but are not committed): no host sync, and a launch
 //     sequence that depends only on the token count.
+// `decode_points` is the automatic mask generator's step: n point prompts against ONE image as one such batch, the
+// prompt-independent image work done once, every mask of a prompt from one pass over its upscaled map, low-res output only.
 #include "engine.h"
 
 namespace sampt {
@@ -112,12 +114,12 @@ struct L {
   size_t skn;
   const std::unordered_map<const float*, const half_t*>* w_hl = nullptr;
   int lin(const float* A, int M, int K, const float* W, const float* b, float* C, int N, int act = ACT_NONE,
-          const float* res = nullptr, int lda = 0) const {
+          const float* res = nullptr, int lda = 0, int res_mod = 0, int ldc = 0) const {
     GemmP p;
-    p.A = A, p.W = W, p.bias = b, p.C = C, p.res = res;
-    p.M = M, p.N = N, p.K = K, p.lda = lda ? lda : K, p.ldw = K, p.ldc = N, p.ldr = N, p.act = act;
+    p.A = A, p.W = W, p.bias = b, p.C = C, p.res = res, p.res_mod = res_mod;   // res_mod: the residual is a block of res_mod rows, broadcast
+    p.M = M, p.N = N, p.K = K, p.lda = lda ? lda : K, p.ldw = K, p.ldc = ldc ? ldc : N, p.ldr = N, p.act = act;
     p.splitk_ws = skws, p.splitk_ws_floats = skn;
-    if (w_hl && M >= 2048 && !lda && K % 32 == 0 && N % 4 == 0) {     // image-token projections, split-fp16 planes packed
+    if (w_hl && M >= 2048 && !lda && !ldc && K % 32 == 0 && N % 4 == 0) {     // image-token projections, split-fp16 planes packed
       auto it = w_hl->find(W);
       if (it != w_hl->end()) {
         p.W = it->second, p.W_lo = it->second + (size_t)N * K;
@@ -476,6 +478,141 @@ int DecEngine::track_decode(int F, const float* features, const float* hq_feat, 
     }
   }
   return sam_finalize_mask(cur_logits, cur_iou, iou_thr, final_logits, score_out, nlog, F, s);
+}
+
+// n point prompts against ONE image (the automatic mask generator's batch): `decode` with F = n, except that
+//   * the image side is shared until the first image -> token attention has run: `features + no_mask_embed` and the layer-0
+//     fused K | V | Q' projection are computed once on g*g rows, the layer-0 token -> image attention is ONE item with n * Nt
+//     queries over those keys, the layer-0 image -> token attention reads the same queries for every item, and its residual is
+//     that one row block broadcast; from there on the image keys are per prompt and the batched kernels apply unchanged;
+//   * all masks of an item come from one pass over its upscaled map (sam_mask_dot_multi), the IoU head writes [n][m];
+//   * nothing is post-processed: low-res masks and IoUs only (amg.hip scores them).
+// multimask: SAM -> m = 3 (mask tokens 1..3); HQ-SAM -> m = 1, the SAM mask of the token with the largest predicted IoU + the
+// HQ mask, that IoU (MaskDecoderHQ.forward, hq_token_only=False; the arg-max is taken on the device).
+int DecEngine::decode_points(int n, const float* features, const float* hq_feat, const float* pts, const int* labels, int k,
+                             bool multi, float* low_out, float* iou_out, Arena& ws, hipStream_t s) {
+  const int g = c.grid, P = g * g, C = c.C, H = c.heads, NO = n_out();
+  const int Nt = NO + k + 1, F = n;
+  if (Nt > 4096 || k <= 0 || F <= 0 || F > max_frames || c.depth < 1) return SAMPT_ERR_UNSUPPORTED;
+  if (is_hq() != (hq_feat != nullptr)) return SAMPT_ERR_ARG;
+  const int inner = C / 2;
+  if (inner != 16 * H || inner != 128) return SAMPT_ERR_UNSUPPORTED;   // attn_t2i / attn_fewkeys: 8 heads x 16 channels
+  const size_t FP = (size_t)F * P, FT = (size_t)F * Nt;
+  const int ms = multi ? 3 : 1;                         // SAM masks / IoUs computed per item
+  Bufs b;
+  b.tokens = ws.f32(FT * C);
+  float* queries = ws.f32(FT * C);
+  b.qin = ws.f32(FT * C);
+  float* keys0 = ws.f32((size_t)P * C);                 // features + no_mask_embed: one image
+  b.kvq = ws.f32(FP * 3 * inner);
+  b.keys = ws.f32(FP * C);
+  b.Q = ws.f32(FT * C), b.K = ws.f32(FT * C), b.V = ws.f32(FT * C);     // token-side projections only (the image side is kvq)
+  b.att = ws.f32(FP * inner > FT * C ? FP * inner : FT * C);
+  b.hid = ws.f32(FT * c.mlp);
+  b.part_floats = attn_t2i_workspace_floats(1, (int)FT, P);            // covers (F, Nt) as well: the bound is the same expression
+  b.part = ws.f32(b.part_floats ? b.part_floats : 4);
+  b.up0 = ws.f32(4 * FP * (C / 4));
+  b.up1 = ws.f32(16 * FP * (C / 8));
+  b.t0 = ws.f32((size_t)F * C), b.t1 = ws.f32((size_t)F * C);
+  float* hyper = ws.f32((size_t)F * ms * (C / 8));
+  float *uh0 = nullptr, *uh1 = nullptr, *t3 = nullptr, *iou3 = nullptr;
+  if (is_hq()) uh0 = ws.f32(16 * FP * (C / 4)), uh1 = ws.f32(16 * FP * (C / 8)), t3 = ws.f32((size_t)F * (C / 8)), iou3 = ws.f32((size_t)F * 4);
+  const size_t skn = (size_t)16 * FT * C;
+  float* skws = ws.f32(skn);
+  if (!ws.ok()) return SAMPT_ERR_WORKSPACE;
+  if (ws.dry()) return SAMPT_OK;
+  L l{s, skws, skn, w_hl.empty() ? nullptr : &w_hl};
+
+  SAMPT_TRY(sam_tokens(out_tokens, NO, pts, labels, k, k, nullptr, gauss, point_emb, not_a_point, (float)c.img, F, nullptr, nullptr,
+                       b.tokens, s));
+  SAMPT_TRY(add_bcast(features, no_mask, keys0, (long)P * C, C, s));
+  const float* qpe = b.tokens;
+  const long nT = (long)FT * C;
+  for (int i = 0; i < c.depth; ++i) {
+    const Layer& Ly = layer[i];
+    if (i == 0) {
+      SAMPT_TRY(attn_block(l, Ly.self, H, C, F, b.tokens, Nt, b.tokens, b.tokens, Nt, false, nullptr, b, nullptr, queries, Ly.n1w,
+                           Ly.n1b, s));
+    } else {
+      SAMPT_TRY(add_bcast(queries, qpe, b.qin, nT, nT, s));
+      SAMPT_TRY(attn_block(l, Ly.self, H, C, F, b.qin, Nt, b.qin, queries, Nt, false, nullptr, b, queries, queries, Ly.n1w, Ly.n1b, s));
+    }
+    SAMPT_TRY(add_bcast(queries, qpe, b.qin, nT, nT, s));
+    SAMPT_TRY(l.lin(b.qin, (int)FT, C, Ly.t2i.qw, Ly.t2i.qb, b.Q, inner));
+    if (i == 0) {      // shared image: P rows projected once, all n * Nt token queries attend to them as one item
+      SAMPT_TRY(fused_proj(l, kvq[0], keys0, (long)P, C, P, b.kvq));
+      SAMPT_TRY(attn_t2i(b.Q, b.kvq, b.kvq + inner, b.att, 1, (int)FT, P, b.part, b.part_floats, s, 3 * inner));
+    } else {
+      SAMPT_TRY(fused_proj(l, kvq[i], b.keys, (long)FP, C, P, b.kvq));
+      SAMPT_TRY(attn_t2i(b.Q, b.kvq, b.kvq + inner, b.att, F, Nt, P, b.part, b.part_floats, s, 3 * inner));
+    }
+    SAMPT_TRY(attn_tail(l, Ly.t2i, C, (long)FT, b.att, queries, queries, Ly.n2w, Ly.n2b, s));
+    SAMPT_TRY(l.lin(queries, (int)FT, C, Ly.m1w, Ly.m1b, b.hid, c.mlp, ACT_RELU));
+    SAMPT_TRY(l.lin(b.hid, (int)FT, c.mlp, Ly.m2w, Ly.m2b, queries, C, ACT_NONE, queries));
+    SAMPT_TRY(layernorm_rows(queries, Ly.n3w, Ly.n3b, queries, (long)FT, C, 1e-5f, nullptr, 0, ACT_NONE, s));
+    SAMPT_TRY(add_bcast(queries, qpe, b.qin, nT, nT, s));
+    SAMPT_TRY(l.lin(b.qin, (int)FT, C, Ly.i2t.kw, Ly.i2t.kb, b.K, inner));
+    SAMPT_TRY(l.lin(queries, (int)FT, C, Ly.i2t.vw, Ly.i2t.vb, b.V, inner));
+    if (i == 0) {      // the same P image queries for every item; keys = LN(keys0 (broadcast) + out_proj(att)) become per prompt
+      SAMPT_TRY(attn_fewkeys(b.kvq + 2 * inner, b.K, b.V, b.att, F, P, Nt, H, inner / H, nullptr, s, 3 * inner, true));
+      SAMPT_TRY(l.lin(b.att, (int)FP, inner, Ly.i2t.ow, Ly.i2t.ob, b.keys, C, ACT_NONE, keys0, 0, P));
+      SAMPT_TRY(layernorm_rows(b.keys, Ly.n4w, Ly.n4b, b.keys, (long)FP, C, 1e-5f, nullptr, 0, ACT_NONE, s));
+    } else {
+      SAMPT_TRY(attn_fewkeys(b.kvq + 2 * inner, b.K, b.V, b.att, F, P, Nt, H, inner / H, nullptr, s, 3 * inner));
+      SAMPT_TRY(attn_tail(l, Ly.i2t, C, (long)FP, b.att, b.keys, b.keys, Ly.n4w, Ly.n4b, s));
+    }
+  }
+  SAMPT_TRY(add_bcast(queries, qpe, b.qin, nT, nT, s));
+  SAMPT_TRY(fused_proj(l, fin_kv, b.keys, (long)FP, C, P, b.kvq));
+  SAMPT_TRY(l.lin(b.qin, (int)FT, C, fin.qw, fin.qb, b.Q, inner));
+  SAMPT_TRY(attn_t2i(b.Q, b.kvq, b.kvq + inner, b.att, F, Nt, P, b.part, b.part_floats, s, 2 * inner));
+  SAMPT_TRY(attn_tail(l, fin, C, (long)FT, b.att, queries, queries, nfw, nfb, s));
+
+  SAMPT_TRY(convt_pair(*this, F, b.keys, C, up0_w, up0_b, C / 4, upln_w, upln_b, up1_w, up1_b, C / 8, ACT_GELU, nullptr, b.up0,
+                       b.up1, nullptr, 0, s, up0_hl, up1_hl));
+  // ---- heads: token row r of every item is a strided-row GEMM operand (lda = Nt * C); hyper [n][ms][C/8]
+  auto mlp3 = [&](int row, const float* const* w, const float* const* bb, float* out, int nout, int ldc, int wrow0) {
+    SAMPT_TRY(l.lin(queries + (size_t)row * C, F, C, w[0], bb[0], b.t0, C, ACT_RELU, nullptr, Nt * C));
+    SAMPT_TRY(l.lin(b.t0, F, C, w[1], bb[1], b.t1, C, ACT_RELU));
+    return l.lin(b.t1, F, C, w[2] + (size_t)wrow0 * C, bb[2] + wrow0, out, nout, ACT_NONE, nullptr, 0, 0, ldc);
+  };
+  const int C8 = C / 8;
+  if (multi) {
+    for (int m = 0; m < 3; ++m) SAMPT_TRY(mlp3(2 + m, hypx_w[m], hypx_b[m], hyper + m * C8, C8, 3 * C8, 0));
+  } else {
+    SAMPT_TRY(mlp3(1, hyp_w, hyp_b, hyper, C8, C8, 0));
+  }
+  const bool select = multi && is_hq();
+  // IoU head: slots 1..3 (multimask) or 0 of iou_prediction_head's last layer, written [n][ms] in place
+  SAMPT_TRY(mlp3(0, iou_w, iou_b, select ? iou3 : iou_out, ms, ms, multi ? 1 : 0));
+  if (!is_hq())
+    return sam_mask_dot_multi(b.up1, hyper, ms, ms, nullptr, nullptr, 0, nullptr, low_out, nullptr, F, 16 * P, C8, s);
+  const int Lr = 4 * g;
+  GemmP p;
+  p.A = b.up1, p.W = hq.mf0_w, p.bias = hq.mf0_b, p.C = uh0;
+  p.M = (int)(16 * FP), p.N = C / 4, p.K = 9 * C8, p.ldw = p.K, p.ldc = C / 4;
+  p.conv = 1, p.cH = Lr, p.cW = Lr, p.cC = C8, p.KH = 3, p.KW = 3, p.cstride = 1, p.cpad = 1, p.OH = Lr, p.OW = Lr;
+  if (hq.mf0_hl) {
+    p.W = hq.mf0_hl, p.W_lo = hq.mf0_hl + (size_t)p.N * p.K, p.alpha = 1.0f / (float)(1 << F16X3_WSHIFT);
+    SAMPT_TRY(conv_f16x3(p, s));
+  } else {
+    SAMPT_TRY(gemm_f32(p, s));
+  }
+  SAMPT_TRY(layernorm_rows(uh0, hq.mfln_w, hq.mfln_b, uh0, 16L * FP, C / 4, 1e-6f, nullptr, 0, ACT_GELU, s));
+  // + hq_features: ONE image's [16 P][C/8] block, broadcast over the items (res_mod)
+  GemmP q;
+  q.A = uh0, q.W = hq.mf1_w, q.bias = hq.mf1_b, q.C = uh1, q.res = hq_feat, q.res_mod = 16 * P;
+  q.M = (int)(16 * FP), q.N = C8, q.K = 9 * (C / 4), q.ldw = q.K, q.ldc = C8, q.ldr = C8;
+  q.conv = 1, q.cH = Lr, q.cW = Lr, q.cC = C / 4, q.KH = 3, q.KW = 3, q.cstride = 1, q.cpad = 1, q.OH = Lr, q.OW = Lr;
+  if (hq.mf1_hl) {
+    q.W = hq.mf1_hl, q.W_lo = hq.mf1_hl + (size_t)q.N * q.K, q.alpha = 1.0f / (float)(1 << F16X3_WSHIFT);
+    SAMPT_TRY(conv_f16x3(q, s));
+  } else {
+    SAMPT_TRY(gemm_f32(q, s));
+  }
+  SAMPT_TRY(mlp3(5, hq.mlp_w, hq.mlp_b, t3, C8, C8, 0));
+  return sam_mask_dot_multi(b.up1, hyper, ms, 1, uh1, t3, C8, select ? iou3 : nullptr, low_out, select ? iou_out : nullptr, F,
+                            16 * P, C8, s);
 }
 
 }  // namespace sampt

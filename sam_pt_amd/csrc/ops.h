@@ -216,10 +216,16 @@ size_t attn_t2i_workspace_floats(int F, int Nq, int Nk);
 int attn_t2i(const float* q, const float* k, const float* v, float* out, int F, int Nq, int Nk, float* ws, size_t ws_floats,
              hipStream_t s, int ldkv = 128 /* row stride of k and v in floats (slices of a fused projection) */);
 int attn_fewkeys(const float* q, const float* k, const float* v, float* out, int F, int Nq, int Nk, int heads, int hd,
-                 const int* nk_item, hipStream_t s, int ldq = 0 /* row stride of q in floats (0: heads*hd) */);
+                 const int* nk_item, hipStream_t s, int ldq = 0 /* row stride of q in floats (0: heads*hd) */,
+                 bool shared_q = false /* q is [Nq][ldq], the same queries for every item (8 heads x 16 channels only) */);
 // low_res[f][p] = <hyper[f][0:C], up[f][p][0:C]>
 int sam_mask_dot(const float* up, const float* hyper, int ld_hyper, const float* up2 /*or null*/, const float* hyper2,
                  int ld_hyper2, float* low_res, int F, int npix, int C, hipStream_t s);
+// every mask of an item from one read of its upscaled map (C == 32): low_res [F][m_out][npix] = <hyper[f][j], up[f][p]>, hyper [F][mh][32],
+// m_out = 3 (needs mh >= 3) or 1.  up2 / hyper2 (HQ-SAM, m_out = 1): the HQ term is added.  sel [F][mh] (with up2): the mask token with the
+// largest sel[f][.] is the one used and iou_sel[f] receives that maximum (MaskDecoderHQ with multimask_output=True)
+int sam_mask_dot_multi(const float* up, const float* hyper, int mh, int m_out, const float* up2, const float* hyper2,
+                       int ld_hyper2, const float* sel, float* low_res, float* iou_sel, int F, int npix, int C, hipStream_t s);
 // fused Sam.postprocess_masks: low (L x L) -> bilinear to (img x img) -> crop (in_h,in_w) -> bilinear to (oh,ow)
 int sam_postprocess(const float* low, int L, int img, int in_h, int in_w, float* out, int oh, int ow, hipStream_t s);
 // bbox state per frame: int[5] = {xmin, ymin, xmax, ymax, count} of logits > 0 (refinement box of sam_pt.py:809-820);
@@ -227,6 +233,15 @@ int sam_postprocess(const float* low, int L, int img, int in_h, int in_w, float*
 size_t bbox_partial_ints(int oh, int ow);
 int sam_postprocess_bbox(const float* low, int L, int img, int in_h, int in_w, float* out, int oh, int ow, int F,
                          int* bbox, int* bbox_partial, hipStream_t s);
+// ---- amg.hip: scoring tail of the automatic mask generator on low-res masks [N][L][L] (no full-resolution logits are written)
+// out8 int [N][8] = {#(v > thr + off), #(v > thr - off), #(v > thr), inclusive XYXY box of v > thr (zeros when empty), 0} of
+// v = Sam.postprocess_masks(low) evaluated on the fly with k_sam_postprocess's arithmetic; ws: amg_score_workspace_bytes(N)
+size_t amg_score_workspace_bytes(int N);
+int amg_score(const float* low, int N, int L, int img, int in_h, int in_w, int oh, int ow, double thr, double off, int* out8,
+              void* ws, size_t ws_bytes, hipStream_t s);
+// out bytes [R][oh][ow] = (v(low[rows[r]]) > thr) as 0 / 1; rows: device int [R] with values in [0, N)
+int amg_binarize(const float* low, int N, const int* rows, int R, int L, int img, int in_h, int in_w, int oh, int ow, double thr,
+                 unsigned char* out, hipStream_t s);
 int bbox_from_logits_state(const float* logits, int h, int w, int* bbox_state, int* bbox_partial, hipStream_t s);
 // mask-input embedding (PromptEncoder.mask_downscaling, App. A-4) fused with "src = image_embedding + dense":
 //   mask (4g x 4g) -> conv2x2s2(1->c1) LN2d GELU -> conv2x2s2(c1->c2) LN2d GELU -> conv1x1(c2->256) ; src = feat + dense

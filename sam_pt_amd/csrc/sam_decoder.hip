@@ -3,6 +3,7 @@
 // so the engine runs pass r of ALL frames as one launch (tokens [F][Nt][256], image tokens [F][4096][256]) instead of
 // F latency-bound single-frame launches.
 #include "ops.h"
+#include "sam_postprocess.h"
 
 namespace sampt {
 
@@ -593,12 +594,12 @@ __global__ __launch_bounds__(256) void k_attn_fewkeys(const float* __restrict__ 
 // loads and stores are whole 512-byte rows.
 __global__ __launch_bounds__(512) void k_attn_fewkeys_s(const float* __restrict__ q, const float* __restrict__ k,
                                                         const float* __restrict__ v, float* __restrict__ out, int Nq,
-                                                        int Nk, const int* __restrict__ nk_item, int ldq) {
+                                                        int Nk, const int* __restrict__ nk_item, int ldq, long q_fs) {
   constexpr int HD = 16, LD = 128, SLD = 132;
   __shared__ float stage[64 * SLD];
   const int f = blockIdx.y, q0 = blockIdx.x * 64, tid = threadIdx.x;
   const int h = __builtin_amdgcn_readfirstlane(tid >> 6), ql = tid & 63;
-  q += (long)f * Nq * ldq, out += (long)f * Nq * LD;
+  q += (long)f * q_fs, out += (long)f * Nq * LD;      // q_fs = Nq * ldq, or 0: every item attends with the same queries
   // wave-uniform pointers in the constant address space: hipcc then always selects scalar loads for them (K and V are
   // written by earlier launches only)
   typedef const __attribute__((address_space(4))) float* cptr;
@@ -654,15 +655,17 @@ __global__ __launch_bounds__(512) void k_attn_fewkeys_s(const float* __restrict_
 }
 
 int attn_fewkeys(const float* q, const float* k, const float* v, float* out, int F, int Nq, int Nk, int heads, int hd,
-                 const int* nk_item, hipStream_t s, int ldq) {
+                 const int* nk_item, hipStream_t s, int ldq, bool shared_q) {
   if (Nk <= 0 || hd != 16 || F <= 0) return SAMPT_ERR_UNSUPPORTED;
   if (ldq == 0) ldq = heads * hd;
   if (ldq < heads * hd || ldq % 4) return SAMPT_ERR_ARG;
   if (heads == 8 && hd == 16) {
-    hipLaunchKernelGGL(k_attn_fewkeys_s, dim3(cdiv(Nq, 64), F), dim3(512), 0, s, q, k, v, out, Nq, Nk, nk_item, ldq);
+    hipLaunchKernelGGL(k_attn_fewkeys_s, dim3(cdiv(Nq, 64), F), dim3(512), 0, s, q, k, v, out, Nq, Nk, nk_item, ldq,
+                       shared_q ? 0L : (long)Nq * ldq);
     SAMPT_CHECK_LAUNCH("attn_fewkeys_s");
     return SAMPT_OK;
   }
+  if (shared_q) return SAMPT_ERR_UNSUPPORTED;
   const int chunk = Nk < 128 ? Nk : 128;
   const bool stage = heads * hd == 128;
   size_t sh = ((size_t)2 * chunk * heads * hd + (stage ? 32 * 132 : 0)) * sizeof(float);
@@ -762,29 +765,68 @@ int sam_mask_dot(const float* up, const float* hyper, int ld_hyper, const float*
   return SAMPT_OK;
 }
 
+// All masks of an item from ONE read of its upscaled map (multimask_output=True; C == 32): low[f][j][p] = <hyper[f][j0 + j], up[f][p]>
+// for j < M, hyper [F][mh][32].  HQ-SAM (up2): M == 1 and low[f][p] += <hyper2[f], up2[f][p]>; with `sel` [F][mh] (the predicted
+// IoUs of the item's mask tokens) j0 = the first arg-max of sel[f] — MaskDecoderHQ's multimask rule, taken on the device — and
+// iou_sel[f] = that maximum.
+template <int M>
+__global__ __launch_bounds__(256) void k_sam_mask_dot_multi(const float* __restrict__ up, const float* __restrict__ hyper, int mh,
+                                                            const float* __restrict__ up2, const float* __restrict__ hyper2,
+                                                            int ld_hyper2, const float* __restrict__ sel,
+                                                            float* __restrict__ low, float* __restrict__ iou_sel, int npix) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int f = blockIdx.y, part = (int)(idx & 7);
+  const long p = idx >> 3;
+  const bool live = p < npix;                      // (npix * 8 is a multiple of the block: whole octets are live or dead)
+  int j0 = 0;
+  if (sel) {
+    float best = sel[(long)f * mh];
+    for (int j = 1; j < mh; ++j) {
+      const float c = sel[(long)f * mh + j];
+      if (c > best) best = c, j0 = j;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) iou_sel[f] = best;
+  }
+  const long pe = ((long)f * npix + (live ? p : 0)) * 32 + part * 4;
+  const float4 t = *(const float4*)(up + pe);
+  float a[M];
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    const float4 h = *(const float4*)(hyper + ((long)f * mh + j0 + j) * 32 + part * 4);
+    a[j] = oct_sum(__builtin_fmaf(h.w, t.w, __builtin_fmaf(h.z, t.z, __builtin_fmaf(h.y, t.y, h.x * t.x))));
+  }
+  if (up2) {
+    const float4 t2 = *(const float4*)(up2 + pe);
+    const float4 h2 = *(const float4*)(hyper2 + (long)f * ld_hyper2 + part * 4);
+    a[0] += oct_sum(h2.x * t2.x + h2.y * t2.y + h2.z * t2.z + h2.w * t2.w);
+  }
+  if (live && part == 0) {
+#pragma unroll
+    for (int j = 0; j < M; ++j) low[((long)f * M + j) * npix + p] = a[j];
+  }
+}
+
+int sam_mask_dot_multi(const float* up, const float* hyper, int mh, int m_out, const float* up2, const float* hyper2,
+                       int ld_hyper2, const float* sel, float* low_res, float* iou_sel, int F, int npix, int C, hipStream_t s) {
+  if (C != 32 || (npix * 8L) % 256 || F <= 0 || mh < 1) return SAMPT_ERR_UNSUPPORTED;
+  if ((m_out != 1 && m_out != 3) || m_out > mh || (up2 && (m_out != 1 || !hyper2 || ld_hyper2 % 4)) ||
+      (sel && (!iou_sel || m_out != 1)) || (((uintptr_t)hyper | (uintptr_t)hyper2 | (uintptr_t)up | (uintptr_t)up2) & 15))
+    return SAMPT_ERR_ARG;
+  const dim3 grid(cdiv((long)npix * 8, 256), F);
+  if (m_out == 3)
+    hipLaunchKernelGGL(k_sam_mask_dot_multi<3>, grid, dim3(256), 0, s, up, hyper, mh, up2, hyper2, ld_hyper2, sel, low_res, iou_sel, npix);
+  else
+    hipLaunchKernelGGL(k_sam_mask_dot_multi<1>, grid, dim3(256), 0, s, up, hyper, mh, up2, hyper2, ld_hyper2, sel, low_res, iou_sel, npix);
+  SAMPT_CHECK_LAUNCH("sam_mask_dot_multi");
+  return SAMPT_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Sam.postprocess_masks fused: low (LxL) --bilinear--> (img x img) --crop (in_h,in_w)--> bilinear --> (oh,ow),
 // both align_corners=False.  Optionally reduces the bounding box / count of logits > 0 (sam_pt.py:809-820) in two
 // deterministic stages (per-workgroup partials, then k_bbox_final): state int[5] = {xmin, ymin, xmax, ymax, count}.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void src_index(int d, float scale, int in, int& i0, int& i1, float& l1) {
-  float src = scale * ((float)d + 0.5f) - 0.5f;
-  if (src < 0.f) src = 0.f;
-  i0 = (int)src;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = fminf(fmaxf(src - (float)i0, 0.f), 1.f);
-}
-
-__device__ __forceinline__ float up_sample(const float* __restrict__ low, int L, float s1, int Y, int X) {
-  int y0, y1, x0, x1;
-  float ly, lx;
-  src_index(Y, s1, L, y0, y1, ly);
-  src_index(X, s1, L, x0, x1, lx);
-  float hy = 1.f - ly, hx = 1.f - lx;
-  return hy * (hx * low[y0 * L + x0] + lx * low[y0 * L + x1]) + ly * (hx * low[y1 * L + x0] + lx * low[y1 * L + x1]);
-}
-
+// (src_index / up_sample: sam_postprocess.h, shared with amg.hip)
 __device__ __forceinline__ void bbox_block_reduce(bool pos, int x, int y, int (*red)[5], int* out5) {
   int xmin = pos ? x : 0x7fffffff, xmax = pos ? x : -1, ymin = pos ? y : 0x7fffffff, ymax = pos ? y : -1;
   int cnt = pos ? 1 : 0;

@@ -8,7 +8,9 @@ What the reference touches on a predictor and therefore what is
 
 Beyond the reference API (used by our own ``SamPt`` for speed, legal inside the same seam — SURVEY.md §7.1):
 ``encode_frames`` (batched image encoding of a whole clip, embeddings stay in HBM) and ``track_decode`` (the whole
-per-(frame, object) prompt chain of ``SamPt.predict_mask`` on device without host syncs).
+per-(frame, object) prompt chain of ``SamPt.predict_mask`` on device without host syncs).  For the automatic mask
+generator: ``predict_points_batch`` (a batch of point prompts against the current image as ONE decoder chain, low-res masks
+only), ``score_masks`` and ``binarize_masks`` (its scoring tail without full-resolution logits).
 """
 from __future__ import annotations
 
@@ -251,6 +253,8 @@ class SamPredictor:
         self._ws_vit: Dict[int, torch.Tensor] = {}
         self._ws_dec: Dict[Tuple[int, int], torch.Tensor] = {}
         self._ws_hq = None
+        self._ws_pts = None
+        self._ws_score = None
         self._stage: Dict[tuple, Dict[str, torch.Tensor]] = {}
         # hipGraph replay of the per-(frame, object) decode chain (sampt_sam_track_decode_graph); SAMPT_DEC_GRAPH=0|1
         self.use_graph = os.environ.get("SAMPT_DEC_GRAPH", "1") != "0"
@@ -291,6 +295,7 @@ class SamPredictor:
                 lib.sampt_dec_destroy(self._dec)
             self._vit = self._dec = None
             self._ws_vit, self._ws_dec, self._ws_hq = {}, {}, None
+            self._ws_pts = self._ws_score = None
             self._stage.clear()
             self._dead_cache.clear()
             self._bias_orig, self._bias_live = None, None
@@ -552,12 +557,11 @@ class SamPredictor:
                       return_logits: bool = False):
         if not self.is_image_set:
             raise RuntimeError("An image must be set with .set_image(...) before mask prediction.")
-        if multimask_output and self.model.hq:
-            raise NotImplementedError("multimask_output=True with the HQ-SAM decoder is not built (SAM-PT never asks for "
-                                      "it: sam_pt.py:787, 796, 805, 826)")
         if point_coords is None:
             raise NotImplementedError("predict_torch: prompts without points are not supported")
         self._ensure()
+        if multimask_output and self.model.hq:
+            return self._predict_torch_hq_multimask(point_coords, point_labels, boxes, mask_input, return_logits)
         dev = self._dev
         oh, ow = self.original_size
         ih, iw = self.input_size
@@ -597,6 +601,136 @@ class SamPredictor:
             self.stats["predict"] += 1
         masks = logits if return_logits else logits > self.model.mask_threshold
         return masks, iou, low
+
+    def _predict_torch_hq_multimask(self, point_coords, point_labels, boxes, mask_input, return_logits):
+        """HQ-SAM with ``multimask_output=True`` (MaskDecoderHQ.forward, hq_token_only=False): ONE mask per prompt — the SAM
+        mask of the mask token (1..3) with the largest predicted IoU + the HQ mask — and that IoU; shapes (B,1,H,W), (B,1),
+        (B,1,4g,4g).  Prompt by prompt, like the loop below (a batch member sees what a single call sees)."""
+        if boxes is not None or mask_input is not None:
+            raise NotImplementedError("predict_torch: HQ-SAM with multimask_output=True takes point prompts only")
+        dev = self._dev
+        oh, ow = self.original_size
+        ih, iw = self.input_size
+        B, L, img = point_coords.shape[0], 4 * self.model.cfg.grid, self.model.cfg.img_size
+        pts = point_coords.to(dev, torch.float32).contiguous()
+        lab = point_labels.to(dev, torch.int32).contiguous()
+        logits = torch.empty((B, 1, oh, ow), dtype=torch.float32, device=dev)
+        iou = torch.empty((B, 1), dtype=torch.float32, device=dev)
+        low = torch.empty((B, 1, L, L), dtype=torch.float32, device=dev)
+        for b in range(B):
+            lw, io = self._decode_points(pts[b:b + 1].clone(), lab[b:b + 1].clone(), True)
+            lg = torch.empty((oh, ow), dtype=torch.float32, device=dev)
+            _lib.check(self._lib.sampt_postprocess_masks(_lib.ptr(lw), L, img, ih, iw, _lib.ptr(lg), oh, ow, _lib.stream_ptr()),
+                       "sampt_postprocess_masks")
+            logits[b, 0].copy_(lg), iou[b].copy_(io[0]), low[b].copy_(lw[0])
+            self.stats["predict"] += 1
+        masks = logits if return_logits else logits > self.model.mask_threshold
+        return masks, iou, low
+
+    def points_workspace_bytes(self, n: int, k: int = 1) -> int:
+        """Scratch bytes of one ``predict_points_batch`` chunk of n prompts with k points each."""
+        self._ensure()
+        nb = C.c_size_t()
+        _lib.check(self._lib.sampt_sam_decode_points_workspace_bytes(self._dec, int(n), int(k), C.byref(nb)),
+                   "sampt_sam_decode_points_workspace_bytes")
+        return nb.value
+
+    def _decode_points(self, pts: torch.Tensor, lab: torch.Tensor, multimask: bool):
+        """One sampt_sam_decode_points call: pts (n,k,2) f32 / lab (n,k) i32 contiguous on the device, n <= max_decode_batch."""
+        n, k = pts.shape[0], pts.shape[1]
+        m = 3 if (multimask and not self.model.hq) else 1
+        L = 4 * self.model.cfg.grid
+        have = self._ws_pts
+        if have is None or have[0] < n or have[1] < k:
+            nn, kk = (n, k) if have is None else (max(n, have[0]), max(k, have[1]))
+            self._ws_pts = (nn, kk, torch.empty(self.points_workspace_bytes(nn, kk), dtype=torch.uint8, device=self._dev))
+        ws = self._ws_pts[2]
+        low = torch.empty((n, m, L, L), dtype=torch.float32, device=self._dev)
+        iou = torch.empty((n, m), dtype=torch.float32, device=self._dev)
+        _lib.check(self._lib.sampt_sam_decode_points(self._dec, n, _lib.ptr(self._feat_tokens), _lib.ptr(self._hq_tokens),
+                                                     _lib.ptr(pts), _lib.ptr(lab), k, 1 if multimask else 0, _lib.ptr(low),
+                                                     _lib.ptr(iou), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                   "sampt_sam_decode_points")
+        return low, iou
+
+    @torch.no_grad()
+    @_lib.on_device(lambda self, *a, **k: self.model.device)
+    def predict_points_batch(self, point_coords: torch.Tensor, point_labels: torch.Tensor, multimask_output: bool = True,
+                             max_chunk: Optional[int] = None):
+        """B point prompts (point_coords (B,k,2) in input-frame pixels, point_labels (B,k)) against the current image as batched
+        decoder chains of up to ``max_decode_batch`` (or ``max_chunk``) prompts: image-side work that does not depend on the
+        prompt runs once per chunk.  -> (low_res (B,m,4g,4g), iou (B,m)), m = 3 for SAM with ``multimask_output`` (mask tokens
+        1..3), else 1 (HQ-SAM with ``multimask_output``: the best-IoU SAM mask + the HQ mask).  No full-resolution logits: see
+        ``score_masks`` / ``binarize_masks``.  Stream-ordered, no host synchronisation."""
+        if not self.is_image_set:
+            raise RuntimeError("An image must be set with .set_image(...) before mask prediction.")
+        self._ensure()
+        dev = self._dev
+        pts = point_coords.to(dev, torch.float32).contiguous()
+        lab = point_labels.to(dev, torch.int32).contiguous()
+        if pts.dim() != 3 or pts.shape[2] != 2 or pts.shape[1] < 1 or tuple(lab.shape) != tuple(pts.shape[:2]):
+            raise ValueError("predict_points_batch: point_coords (B,k,2) with k >= 1 and point_labels (B,k) expected")
+        if pts.shape[1] > self.max_prompt_points:
+            raise ValueError(f"predict_points_batch: at most {self.max_prompt_points} points per prompt")
+        B = pts.shape[0]
+        step = self.model.max_decode_batch if not max_chunk else max(1, min(int(max_chunk), self.model.max_decode_batch))
+        m, L = (3 if (multimask_output and not self.model.hq) else 1), 4 * self.model.cfg.grid
+        if B <= step:
+            if B == 0:
+                return (torch.empty((0, m, L, L), dtype=torch.float32, device=dev), torch.empty((0, m), dtype=torch.float32, device=dev))
+            low, iou = self._decode_points(pts, lab, multimask_output)
+        else:
+            parts = [self._decode_points(pts[i:i + step], lab[i:i + step], multimask_output) for i in range(0, B, step)]
+            low, iou = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+        self.stats["predict"] += B
+        return low, iou
+
+    @torch.no_grad()
+    @_lib.on_device(lambda self, *a, **k: self.model.device)
+    def score_masks(self, low_res: torch.Tensor, offset: float) -> torch.Tensor:
+        """low_res (N,4g,4g) low-res masks of the current image -> int32 (N,8): per mask ``[hi, lo, area, x0, y0, x1, y1, 0]`` of
+        its full-resolution logits v = ``postprocess_masks(low_res)``, which are evaluated on the fly and never written:
+        hi = #(v > thr + offset), lo = #(v > thr - offset) (stability score = hi / lo), area = #(v > thr) and the inclusive XYXY
+        box of v > thr (zeros for an empty mask, as ``batched_mask_to_box``); thr = ``model.mask_threshold``."""
+        if not self.is_image_set:
+            raise RuntimeError("An image must be set with .set_image(...) before mask scoring.")
+        self._ensure()
+        dev, L = self._dev, 4 * self.model.cfg.grid
+        low = low_res.to(dev, torch.float32).reshape(-1, L, L).contiguous()
+        N = low.shape[0]
+        out = torch.zeros((N, 8), dtype=torch.int32, device=dev)
+        if N == 0:
+            return out
+        if self._ws_score is None or self._ws_score[0] < N:
+            self._ws_score = (N, torch.empty(max(1, self._lib.sampt_amg_score_workspace_bytes(N)), dtype=torch.uint8, device=dev))
+        ws = self._ws_score[1]
+        (oh, ow), (ih, iw) = self.original_size, self.input_size
+        _lib.check(self._lib.sampt_amg_score(_lib.ptr(low), N, L, self.model.cfg.img_size, ih, iw, oh, ow,
+                                             float(self.model.mask_threshold), float(offset), _lib.ptr(out), _lib.ptr(ws),
+                                             ws.numel(), _lib.stream_ptr()), "sampt_amg_score")
+        return out
+
+    @torch.no_grad()
+    @_lib.on_device(lambda self, *a, **k: self.model.device)
+    def binarize_masks(self, low_res: torch.Tensor, rows) -> torch.Tensor:
+        """bool (len(rows),H,W): ``postprocess_masks(low_res[rows]) > model.mask_threshold`` for the listed rows of low_res
+        (N,4g,4g) only, written as a boolean tensor directly (no logits)."""
+        if not self.is_image_set:
+            raise RuntimeError("An image must be set with .set_image(...) before mask binarisation.")
+        self._ensure()
+        dev, L = self._dev, 4 * self.model.cfg.grid
+        low = low_res.to(dev, torch.float32).reshape(-1, L, L).contiguous()
+        idx = torch.as_tensor(rows, device=dev).reshape(-1).to(torch.int32).contiguous()
+        (oh, ow), (ih, iw) = self.original_size, self.input_size
+        out = torch.empty((idx.shape[0], oh, ow), dtype=torch.bool, device=dev)
+        if idx.shape[0] == 0:
+            return out
+        if low.shape[0] == 0:
+            raise ValueError("binarize_masks: rows given but low_res is empty")
+        _lib.check(self._lib.sampt_amg_binarize(_lib.ptr(low), low.shape[0], _lib.ptr(idx), idx.shape[0], L,
+                                                self.model.cfg.img_size, ih, iw, oh, ow, float(self.model.mask_threshold),
+                                                _lib.ptr(out), _lib.stream_ptr()), "sampt_amg_binarize")
+        return out
 
     def predict(self, point_coords=None, point_labels=None, box=None, mask_input=None, multimask_output=True,
                 return_logits=False):
