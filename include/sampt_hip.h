@@ -360,6 +360,27 @@ int sampt_amg_score(const float* low_res_dev, int n_masks, int L, int img_size, 
                     sampt_stream_t stream);
 int sampt_amg_binarize(const float* low_res_dev, int n_masks, const int32_t* rows_dev, int n_rows, int L, int img_size, int in_h,
                        int in_w, int out_h, int out_w, double mask_threshold, uint8_t* out_dev, sampt_stream_t stream);
+/* Tail of the automatic mask generator on the device; both equal the host functions of sam_pt_amd/automatic_mask_generator.py
+ * exactly (integer / threshold logic, no tolerance).
+ * regions: remove_small_regions(m, min_area, "holes") then (., min_area, "islands") of masks_in_dev bytes [n][h][w] (0 / non-0):
+ *   8-connected components; a component is small when it has fewer than min_area pixels; small background components are
+ *   filled, then small foreground components are removed — the largest survives when all are small, among equals the one
+ *   whose first pixel comes first in raster order.  masks_out_dev bytes [n][h][w] (0 / 1; may alias masks_in_dev),
+ *   changed_out_dev bytes [n] (either pass found a small component), area_out_dev int32 [n], boxes_out_dev int32 [n][4]
+ *   inclusive XYXY (zeros for an empty mask).  Labels are the smallest linear pixel index of a component and all sums are
+ *   integer: bitwise reproducible.  h * w < 2^31.  The workspace (16-byte aligned) holds 8 bytes per pixel + 1040 bytes per
+ *   mask in flight; with less than n masks' worth the stack is processed in chunks, with less than one mask's the call fails.
+ * nms: boxes_dev f32 [n][4] XYXY (16-byte aligned), scores_dev f32 [n], n <= 65535.  Sweep in stable decreasing score order;
+ *   a box is dropped when inter / ((area_i + area_j) - inter) > iou_thr with an already kept box, every operation rounded
+ *   to f32 separately (0 / 0 = nan never suppresses).  keep_out_dev int64 [n]: the kept input indices in sweep order, the
+ *   first *count_out_dev (int32 [1]) entries are valid. */
+size_t sampt_amg_regions_workspace_bytes(int n_masks, int h, int w);
+int sampt_amg_regions(const uint8_t* masks_in_dev, int n, int h, int w, int min_area, uint8_t* masks_out_dev,
+                      uint8_t* changed_out_dev, int32_t* area_out_dev, int32_t* boxes_out_dev, void* workspace_dev,
+                      size_t workspace_bytes, sampt_stream_t stream);
+size_t sampt_amg_nms_workspace_bytes(int n);
+int sampt_amg_nms(const float* boxes_dev, const float* scores_dev, int n, float iou_thr, int64_t* keep_out_dev,
+                  int32_t* count_out_dev, void* workspace_dev, size_t workspace_bytes, sampt_stream_t stream);
 /* Whole SamPt.predict_mask chain (sam_pt.py:760-837) for `frames` independent (frame, object) items that share the
  * visible-point count k, batched into one launch sequence and without host synchronisation:
  * [positives-only pass over the first n_pos_first points when n_pos_first >= 0, i.e. negative_points_per_mask > 0;

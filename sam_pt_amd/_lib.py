@@ -79,6 +79,10 @@ _SIGS = {
     "sampt_amg_score_workspace_bytes": (c_size_t, [c_int]),
     "sampt_amg_score": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, C.c_double, C.c_double, _P, _P, c_size_t, _P]),
     "sampt_amg_binarize": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, C.c_double, _P, _P]),
+    "sampt_amg_regions_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "sampt_amg_regions": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "sampt_amg_nms_workspace_bytes": (c_size_t, [c_int]),
+    "sampt_amg_nms": (c_int, [_P, _P, c_int, c_float, _P, _P, _P, c_size_t, _P]),
     "sampt_sam_track_decode": (c_int, [_P, c_int, _P, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_float, c_int, c_int, c_int,
                                        c_int, _P, _P, _P, c_size_t, _P]),
     "sampt_sam_track_decode_graph": (c_int, [_P, c_int, _P, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_float, c_int, c_int,

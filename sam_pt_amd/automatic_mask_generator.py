@@ -27,9 +27,17 @@ Two paths through a batch of points, chosen by ``fused``:
   * ``fused=False`` (and any predictor without ``predict_points_batch``, e.g. the CPU oracle): ``predict_torch`` prompt by
     prompt (``sampt_sam_decode_multimask``) and device tensor work on the full-resolution logits.
 
+The tail after the survivors' masks — box NMS inside a crop and across crops, the small-region clean-up and its re-NMS — runs
+on the device too when the masks live there (``device_tail``): ``nms_device`` (``sampt_amg_nms``: bit matrix of IoU > thr by
+wave ballots, one workgroup sweeps it) and ``remove_small_regions_device`` (``sampt_amg_regions``: 8-connected labelling by
+union-find with min-index roots, holes then islands, area and box of the result).  Both are integer / threshold logic and equal
+the host functions ``nms`` / ``remove_small_regions`` of this file exactly; those stay as the yardsticks and as the host tail
+(``device_tail=False``, and every predictor that is not on a HIP device).
+
 Parity: the helpers are pinned against transformers' independent port of the same
 utilities (tests/test_oracle_pins.py); box NMS restates torchvision's ``batched_nms`` (absent) and the small-region
-clean-up uses ``scipy.ndimage.label`` where upstream uses OpenCV (absent): **those two are parity-unpinned**.
+clean-up uses ``scipy.ndimage.label`` where upstream uses OpenCV (absent): **those two restatements are parity-unpinned**
+against their originals; the device kernels are pinned on the restatements (tests/test_gpu_amg_tail.py, exact equality).
 """
 from __future__ import annotations
 
@@ -216,6 +224,67 @@ def remove_small_regions(mask: np.ndarray, area_thresh: float, mode: str) -> Tup
 
 
 # --------------------------------------------------------------------------------------------------------------------
+# the same two steps on the device (csrc/amg_tail.hip); no CPU fallback
+# --------------------------------------------------------------------------------------------------------------------
+_REGIONS_WS_CAP = 1 << 30          # workspace of one clean-up call; larger stacks are processed in chunks inside the call
+
+
+def nms_device(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float) -> torch.Tensor:
+    """``nms`` on the HIP device: the same indices (int64, on the boxes' device).  One host read: the count."""
+    from . import _lib
+    _lib.require_hip(boxes.device, "nms_device")
+    _lib.require_hip(scores.device, "nms_device")
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or scores.dim() != 1 or scores.shape[0] != boxes.shape[0]:
+        raise _lib.SamptError(f"nms_device: boxes must be (n, 4) and scores (n); got {tuple(boxes.shape)} and {tuple(scores.shape)}")
+    n = boxes.shape[0]
+    if n == 0:
+        return torch.zeros(0, dtype=torch.int64, device=boxes.device)
+    lib = _lib.load()
+    with _lib.device_guard(boxes.device):
+        b = boxes.float().contiguous()
+        sc = scores.to(boxes.device).float().contiguous()
+        keep = torch.empty(n, dtype=torch.int64, device=b.device)
+        count = torch.empty(1, dtype=torch.int32, device=b.device)
+        ws = torch.empty(max(16, lib.sampt_amg_nms_workspace_bytes(n)), dtype=torch.uint8, device=b.device)
+        _lib.check(lib.sampt_amg_nms(_lib.ptr(b), _lib.ptr(sc), n, float(iou_threshold), _lib.ptr(keep), _lib.ptr(count),
+                                     _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "sampt_amg_nms")
+        return keep[:int(count.item())]
+
+
+def remove_small_regions_device(masks: torch.Tensor, min_area: float, workspace_bytes: Optional[int] = None):
+    """``remove_small_regions(m, min_area, "holes")`` then ``(., min_area, "islands")`` of every mask of a bool (N, H, W) HIP
+    tensor -> (masks bool (N, H, W), changed bool (N) = either pass changed something, areas int64 (N), boxes int64 (N, 4) as
+    ``batched_mask_to_box``).  ``workspace_bytes`` bounds the scratch memory (default: the whole stack, at most 1 GiB); a stack
+    that needs more is processed in chunks inside the call."""
+    from . import _lib
+    _lib.require_hip(masks.device, "remove_small_regions_device")
+    if masks.dtype != torch.bool or masks.dim() != 3:
+        raise _lib.SamptError(f"remove_small_regions_device: a bool (N, H, W) tensor is required; got {masks.dtype} "
+                              f"{tuple(masks.shape)}")
+    n, h, w = masks.shape
+    dev = masks.device
+    if n == 0 or h == 0 or w == 0:
+        return (masks.clone(), torch.zeros(n, dtype=torch.bool, device=dev), torch.zeros(n, dtype=torch.int64, device=dev),
+                torch.zeros((n, 4), dtype=torch.int64, device=dev))
+    lib = _lib.load()
+    thr = int(min(max(math.ceil(min_area), 0), 2 ** 31 - 1))           # integer sizes: s < t  <=>  s < ceil(t)
+    with _lib.device_guard(dev):
+        m = masks.contiguous()
+        out = torch.empty_like(m)
+        changed = torch.empty(n, dtype=torch.bool, device=dev)
+        area = torch.empty(n, dtype=torch.int32, device=dev)
+        boxes = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        if workspace_bytes is None:
+            workspace_bytes = min(lib.sampt_amg_regions_workspace_bytes(n, h, w), _REGIONS_WS_CAP)
+            workspace_bytes = max(workspace_bytes, lib.sampt_amg_regions_workspace_bytes(1, h, w))
+        ws = torch.empty(max(16, int(workspace_bytes)), dtype=torch.uint8, device=dev)
+        _lib.check(lib.sampt_amg_regions(_lib.ptr(m), n, h, w, thr, _lib.ptr(out), _lib.ptr(changed), _lib.ptr(area),
+                                         _lib.ptr(boxes), _lib.ptr(ws), int(workspace_bytes), _lib.stream_ptr()),
+                   "sampt_amg_regions")
+    return out, changed, area.to(torch.int64), boxes.to(torch.int64)
+
+
+# --------------------------------------------------------------------------------------------------------------------
 class _MaskData:
     """Parallel per-mask columns (device tensors) that are filtered and concatenated together."""
 
@@ -244,14 +313,17 @@ class SamAutomaticMaskGenerator:
     """Constructor keywords of configs/vis_eval_root.yaml:13-28 (= upstream's).  ``predictor`` (tests) injects any object
     with the ``SamPredictor`` interface instead of building one from ``model``.  ``fused``: None = the batched decode + fused
     scoring path when the predictor offers it (``predict_points_batch`` / ``score_masks`` / ``binarize_masks``), False = always
-    ``predict_torch`` and tensor work on full-resolution logits, True = insist on the fused path."""
+    ``predict_torch`` and tensor work on full-resolution logits, True = insist on the fused path.  ``device_tail``: None = box
+    NMS and the small-region clean-up on the device when the predictor's tensors live on a HIP device, False = the host
+    functions, True = insist on the device tail."""
 
     def __init__(self, model, points_per_side: Optional[int] = 32, points_per_batch: int = 64,
                  pred_iou_thresh: float = 0.88, stability_score_thresh: float = 0.95, stability_score_offset: float = 1.0,
                  box_nms_thresh: float = 0.7, crop_n_layers: int = 0, crop_nms_thresh: float = 0.7,
                  crop_overlap_ratio: float = 512 / 1500, crop_n_points_downscale_factor: int = 1,
                  point_grids: Optional[List[np.ndarray]] = None, min_mask_region_area: int = 0,
-                 output_mode: str = "binary_mask", predictor=None, fused: Optional[bool] = None) -> None:
+                 output_mode: str = "binary_mask", predictor=None, fused: Optional[bool] = None,
+                 device_tail: Optional[bool] = None) -> None:
         if (points_per_side is None) == (point_grids is None):
             raise ValueError("Exactly one of points_per_side or point_grids must be provided.")
         if points_per_side is not None:
@@ -276,6 +348,14 @@ class SamAutomaticMaskGenerator:
             raise ValueError(f"fused=True needs a predictor with predict_points_batch / score_masks / binarize_masks; "
                              f"{type(predictor).__name__} has none (use fused=None or False)")
         self.fused = can_fuse if fused is None else bool(fused)
+        on_hip = getattr(self._device, "type", None) == "cuda"
+        if device_tail and not on_hip:
+            raise ValueError(f"device_tail=True needs a predictor on a HIP device; {type(predictor).__name__} is on "
+                             f"{self._device} (use device_tail=None or False)")
+        if device_tail is None:
+            from . import _lib
+            device_tail = on_hip and all(hasattr(_lib.load(), f) for f in ("sampt_amg_nms", "sampt_amg_regions"))
+        self.device_tail = bool(device_tail)
         self.points_per_batch = points_per_batch
         self.pred_iou_thresh = pred_iou_thresh
         self.stability_score_thresh = stability_score_thresh
@@ -300,9 +380,10 @@ class SamAutomaticMaskGenerator:
         predicted IoU within a crop."""
         data = self._generate_masks(image)
         if self.min_mask_region_area > 0 and len(data):
-            data = self._postprocess_small_regions(data, self.min_mask_region_area,
-                                                   max(self.box_nms_thresh, self.crop_nms_thresh))
+            post = self._postprocess_small_regions_device if self.device_tail else self._postprocess_small_regions
+            data = post(data, self.min_mask_region_area, max(self.box_nms_thresh, self.crop_nms_thresh))
         masks = data["masks"].cpu() if len(data) else torch.zeros((0,) + tuple(image.shape[:2]), dtype=torch.bool)
+        areas = data["area"].cpu().tolist() if self.device_tail else None          # (the host tail sums every mask below)
         boxes, crops = data["boxes"].cpu(), data["crop_boxes"].cpu()
         ious, stab, pts = data["iou_preds"].cpu(), data["stability_score"].cpu(), data["points"].cpu()
         rles = mask_to_rle(masks) if self.output_mode != "binary_mask" and len(masks) else None
@@ -310,7 +391,7 @@ class SamAutomaticMaskGenerator:
         for i in range(masks.shape[0]):
             records.append({
                 "segmentation": masks[i].numpy() if rles is None else rles[i],
-                "area": int(masks[i].sum()),
+                "area": int(masks[i].sum()) if areas is None else int(areas[i]),
                 "bbox": box_xyxy_to_xywh(boxes[i].tolist()),
                 "predicted_iou": float(ious[i]),
                 "point_coords": [pts[i].tolist()],
@@ -319,8 +400,18 @@ class SamAutomaticMaskGenerator:
             })
         return records
 
+    def _nms(self, boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float) -> torch.Tensor:
+        return (nms_device if self.device_tail else nms)(boxes, scores, iou_threshold)
+
     def _empty(self, h: int, w: int) -> _MaskData:
         dev = self._device
+        data = self._empty_host_columns(h, w, dev)
+        if self.device_tail:                                        # the pixel count travels with the mask (device tail only)
+            data["area"] = torch.zeros(0, dtype=torch.int64, device=dev)
+        return data
+
+    @staticmethod
+    def _empty_host_columns(h: int, w: int, dev) -> _MaskData:
         return _MaskData(masks=torch.zeros((0, h, w), dtype=torch.bool, device=dev),
                          iou_preds=torch.zeros(0, device=dev), points=torch.zeros((0, 2), dtype=torch.float64, device=dev),
                          stability_score=torch.zeros(0, device=dev),
@@ -336,7 +427,7 @@ class SamAutomaticMaskGenerator:
         if len(crop_boxes) > 1 and len(data):                       # duplicates across crops: the smaller crop wins
             cb = data["crop_boxes"].float()
             scores = 1.0 / ((cb[:, 2] - cb[:, 0]) * (cb[:, 3] - cb[:, 1]))
-            data.filter(nms(data["boxes"].float(), scores, self.crop_nms_thresh))
+            data.filter(self._nms(data["boxes"].float(), scores, self.crop_nms_thresh))
         return data
 
     def _process_crop(self, image: np.ndarray, crop_box: List[int], layer: int, orig_size: Tuple[int, int]) -> _MaskData:
@@ -351,7 +442,7 @@ class SamAutomaticMaskGenerator:
         for i in range(0, len(points), self.points_per_batch):
             data.cat(process(points[i:i + self.points_per_batch], crop_hw, crop_box, orig_size))
         self.predictor.reset_image()
-        data.filter(nms(data["boxes"].float(), data["iou_preds"], self.box_nms_thresh))
+        data.filter(self._nms(data["boxes"].float(), data["iou_preds"], self.box_nms_thresh))
         data["boxes"] = uncrop_boxes_xyxy(data["boxes"], crop_box)
         data["points"] = uncrop_points(data["points"], crop_box)
         data["crop_boxes"] = torch.tensor([crop_box] * len(data), dtype=torch.int64,
@@ -377,6 +468,8 @@ class SamAutomaticMaskGenerator:
         if self.stability_score_thresh > 0.0:
             data.filter(data["stability_score"] >= self.stability_score_thresh)
         data["masks"] = data["masks"] > thr
+        if self.device_tail:
+            data["area"] = data["masks"].flatten(-2).sum(-1)
         data["boxes"] = batched_mask_to_box(data["masks"])
         keep = ~is_box_near_crop_edge(data["boxes"], crop_box, [0, 0, orig_w, orig_h])
         if not bool(keep.all()):
@@ -411,6 +504,8 @@ class SamAutomaticMaskGenerator:
         masks = self.predictor.binarize_masks(low, data["rows"])
         out = _MaskData(masks=uncrop_masks(masks, crop_box, orig_h, orig_w), iou_preds=data["iou_preds"], points=data["points"],
                         stability_score=data["stability_score"], boxes=data["boxes"])
+        if self.device_tail:
+            out["area"] = data["rec"][:, 2].to(torch.int64)
         return out
 
     @staticmethod
@@ -431,5 +526,18 @@ class SamAutomaticMaskGenerator:
         changed = scores_t == 0.0
         data["masks"] = torch.where(changed[:, None, None], masks, data["masks"])
         data["boxes"] = torch.where(changed[:, None], boxes, data["boxes"])
+        data.filter(keep)
+        return data
+
+    @staticmethod
+    def _postprocess_small_regions_device(data: _MaskData, min_area: int, nms_thresh: float) -> _MaskData:
+        """``_postprocess_small_regions`` without the host: one clean-up call for the stack, the re-NMS with the 0 / 1
+        "unchanged" scores (nearly all tied: the stable order decides) on the device, area and box of the changed rows from the
+        clean-up itself."""
+        masks, changed, areas, boxes = remove_small_regions_device(data["masks"], min_area)
+        keep = nms_device(boxes.float(), (~changed).float(), nms_thresh)
+        data["masks"] = masks                                       # (an unchanged row comes back as it went in)
+        data["boxes"] = torch.where(changed[:, None], boxes, data["boxes"])
+        data["area"] = torch.where(changed, areas, data["area"])
         data.filter(keep)
         return data

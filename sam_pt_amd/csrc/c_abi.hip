@@ -592,6 +592,27 @@ int sampt_amg_binarize(const float* low, int n_masks, const int32_t* rows, int n
   return rc == SAMPT_OK ? rc : fail(rc, "sampt_amg_binarize: bad arguments");
 }
 
+size_t sampt_amg_regions_workspace_bytes(int n_masks, int h, int w) { return amg_regions_workspace_bytes(n_masks, h, w); }
+
+int sampt_amg_regions(const uint8_t* masks_in, int n, int h, int w, int min_area, uint8_t* masks_out, uint8_t* changed_out,
+                      int32_t* area_out, int32_t* boxes_out, void* ws, size_t ws_bytes, sampt_stream_t stream) {
+  if (n < 0 || h <= 0 || w <= 0) return fail(SAMPT_ERR_ARG, "sampt_amg_regions: bad shape");
+  if ((long)h * w >= (1L << 31)) return fail(SAMPT_ERR_ARG, "sampt_amg_regions: h * w must be below 2^31");
+  int rc = amg_regions(masks_in, n, h, w, min_area, masks_out, changed_out, (int*)area_out, (int*)boxes_out, ws, ws_bytes,
+                       (hipStream_t)stream);
+  if (rc == SAMPT_ERR_WORKSPACE) return fail(rc, "sampt_amg_regions: workspace too small for one mask");
+  return rc == SAMPT_OK ? rc : fail(rc, "sampt_amg_regions: null or misaligned pointer");
+}
+
+size_t sampt_amg_nms_workspace_bytes(int n) { return amg_nms_workspace_bytes(n); }
+
+int sampt_amg_nms(const float* boxes, const float* scores, int n, float iou_thr, int64_t* keep_out, int32_t* count_out, void* ws,
+                  size_t ws_bytes, sampt_stream_t stream) {
+  int rc = amg_nms(boxes, scores, n, iou_thr, (long long*)keep_out, (int*)count_out, ws, ws_bytes, (hipStream_t)stream);
+  if (rc == SAMPT_ERR_WORKSPACE) return fail(rc, "sampt_amg_nms: workspace too small");
+  return rc == SAMPT_OK ? rc : fail(rc, "sampt_amg_nms: bad arguments (n outside 0..65535, null or misaligned pointer)");
+}
+
 int sampt_sam_track_decode(sampt_dec_t h, int frames, const float* features, const float* hq_features,
                            const float* pts, const int32_t* labels, int k, const int32_t* k_item,
                            const int32_t* npos_item, int ld_pts, int n_pos_first, int refine_iters, float iou_thr,

@@ -242,6 +242,17 @@ int amg_score(const float* low, int N, int L, int img, int in_h, int in_w, int o
 // out bytes [R][oh][ow] = (v(low[rows[r]]) > thr) as 0 / 1; rows: device int [R] with values in [0, N)
 int amg_binarize(const float* low, int N, const int* rows, int R, int L, int img, int in_h, int in_w, int oh, int ow, double thr,
                  unsigned char* out, hipStream_t s);
+// ---- amg_tail.hip: the generator's tail on the device, exactly the host functions' results
+// small-region clean-up (holes, then islands; 8-connected; small = fewer than min_area pixels) of byte masks [n][h][w] ->
+// masks_out bytes, changed bytes [n], area int [n], boxes int [n][4] (inclusive XYXY, zeros when empty).  The stack is processed
+// in chunks of what ws holds (amg_regions_workspace_bytes(1, h, w) at least)
+size_t amg_regions_workspace_bytes(int n, int h, int w);
+int amg_regions(const unsigned char* masks_in, int n, int h, int w, int min_area, unsigned char* masks_out, unsigned char* changed,
+                int* area, int* boxes, void* ws, size_t ws_bytes, hipStream_t s);
+// greedy box NMS: boxes f32 [n][4] XYXY, scores f32 [n] -> keep (input indices in sweep order), count [1]
+size_t amg_nms_workspace_bytes(int n);
+int amg_nms(const float* boxes, const float* scores, int n, float thr, long long* keep, int* count, void* ws, size_t ws_bytes,
+            hipStream_t s);
 int bbox_from_logits_state(const float* logits, int h, int w, int* bbox_state, int* bbox_partial, hipStream_t s);
 // mask-input embedding (PromptEncoder.mask_downscaling, App. A-4) fused with "src = image_embedding + dense":
 //   mask (4g x 4g) -> conv2x2s2(1->c1) LN2d GELU -> conv2x2s2(c1->c2) LN2d GELU -> conv1x1(c2->256) ; src = feat + dense

@@ -4,6 +4,10 @@ points, 64 per batch): the fused path (batched decode + scoring on low-res masks
 prompt + tensor work on full-resolution logits), alternating in one process.
 
   python tools/amg_bench.py [--model vit_h|vit_b] [--hq] [--repeats 5] [--warmup 1] [--offset 0.02]
+  python tools/amg_bench.py --tail both --min-area 100 [...]   # the tail after the survivors' masks (box NMS, small-region clean-up):
+                                                   # device_tail=True against False on the fused path, alternating, + the two steps alone
+  python tools/amg_bench.py --standalone [--masks 100] [--min-area 100]   # the two steps alone on seeded inputs, no model: clean-up of
+                                                   # blob masks (device call against the host loop), NMS at n = 300, 1000, 3072
   python tools/amg_bench.py --launches [...]      # kernel launches / copies of ONE batch of 64 points on either path (torch.profiler)
   rocprofv3 --kernel-trace --stats -d DIR -o amg -- python tools/amg_bench.py --only fused --repeats 1 --warmup 0
                                                    # then tools/rocprof_summary.py / tools/rocprof_by_grid.py on the .db
@@ -39,14 +43,103 @@ ap.add_argument("--height", type=int, default=576)
 ap.add_argument("--width", type=int, default=1024)
 ap.add_argument("--launches", action="store_true")
 ap.add_argument("--only", default="both", choices=["both", "fused", "unfused"], help="time one path alone (e.g. under a kernel trace)")
+ap.add_argument("--min-area", type=int, default=0, help="min_mask_region_area of generate() (0: no small-region clean-up, the VIS setting)")
+ap.add_argument("--tail", default="device", choices=["both", "device", "host"],
+                help="box NMS / clean-up on the device, on the host, or both alternating on the fused path")
+ap.add_argument("--standalone", action="store_true", help="time the clean-up and NMS alone on seeded inputs (no model)")
+ap.add_argument("--masks", type=int, default=100, help="--standalone: number of blob masks")
 args = ap.parse_args()
 
 dev = torch.device("cuda:0")
+sync = torch.cuda.synchronize
+HBM_GBS = 8000.0        # MI355X HBM3E peak, the figure DESIGN.md quotes for the bandwidth-shaped kernels
+REGION_BYTES_PER_PIXEL = 48
+
+
+def stats(t):
+    return f"median {statistics.median(t):.3f} ms, min {min(t):.3f}, max {max(t):.3f} (spread {max(t) - min(t):.3f})"
+
+
+def timed(fn, repeats, warmup=1):
+    out = []
+    for r in range(warmup + repeats):
+        sync()
+        t0 = time.perf_counter()
+        fn()
+        sync()
+        if r >= warmup:
+            out.append((time.perf_counter() - t0) * 1e3)
+    return out
+
+
+def blob_masks(n, h, w, seed):
+    """The seeded masks of tests/test_amg_tail_cpu.py: upsampled noise > 0.3, 0.4 % speckle, six stamped squares per mask."""
+    g = torch.Generator().manual_seed(seed)
+    z = torch.randn(n, 1, h // 8 + 2, w // 8 + 2, generator=g)
+    m = torch.nn.functional.interpolate(z, size=(h, w), mode="bilinear", align_corners=False)[:, 0] > 0.3
+    m = m ^ (torch.rand(n, h, w, generator=g) < 0.004)
+    for i in range(n):
+        for _ in range(6):
+            s = int(torch.randint(2, 12, (1,), generator=g))
+            y = int(torch.randint(0, max(1, h - s + 1), (1,), generator=g))
+            x = int(torch.randint(0, max(1, w - s + 1), (1,), generator=g))
+            m[i, y:y + s, x:x + s] = bool(torch.randint(0, 2, (1,), generator=g))
+    return m
+
+
+def host_cleanup(masks, min_area):
+    """The clean-up as the host tail runs it: masks to the host, two labellings per mask, masks back, boxes."""
+    out = []
+    for m in masks.cpu().numpy():
+        m, _ = A.remove_small_regions(m, min_area, mode="holes")
+        m, _ = A.remove_small_regions(m, min_area, mode="islands")
+        out.append(torch.as_tensor(m))
+    return A.batched_mask_to_box(torch.stack(out).to(masks.device))
+
+
+def bench_cleanup(masks, min_area, repeats, host=True):
+    n, h, w = masks.shape
+    if n == 0:
+        print("clean-up alone: no masks survive, nothing to time")
+        return
+    nbytes = n * h * w * REGION_BYTES_PER_PIXEL
+    t_dev = timed(lambda: A.remove_small_regions_device(masks, min_area), repeats)
+    gbs = nbytes / (statistics.median(t_dev) * 1e-3) / 1e9
+    print(f"clean-up alone, {n} masks of {h} x {w}, min_area {min_area}: device {stats(t_dev)}")
+    print(f"  byte count {nbytes / 1e6:.1f} MB = {REGION_BYTES_PER_PIXEL} B per pixel (per pass: mask 1 B read + 1 B written, label 4 B written + read "
+          f"twice - three times in the islands pass -, size 4 B zeroed + 4 B read; chain reads, compress writes and atomics not counted) "
+          f"-> {gbs:.0f} GB/s = {100 * gbs / HBM_GBS:.1f} % of the {HBM_GBS:.0f} GB/s HBM peak")
+    if host:
+        t_host = timed(lambda: host_cleanup(masks, min_area), repeats)
+        a, b = statistics.median(t_host), statistics.median(t_dev)
+        print(f"  host loop (copy, scipy.ndimage.label twice per mask, copy back, boxes): {stats(t_host)}")
+        print(f"  host - device = {a - b:.1f} ms ({a / b:.0f} x); sum of both spreads {max(t_host) - min(t_host) + max(t_dev) - min(t_dev):.1f} ms")
+
+
+def bench_nms(n, repeats, thr=0.7, seed=5):
+    g = torch.Generator().manual_seed(seed + n)
+    xy = torch.rand(n, 2, generator=g) * (40.0 + 0.15 * n)
+    boxes = torch.cat([xy, xy + torch.rand(n, 2, generator=g) * 30.0], dim=1).to(dev)
+    scores = torch.rand(n, generator=g).to(dev)
+    t_dev = timed(lambda: A.nms_device(boxes, scores, thr), repeats)
+    t_host = timed(lambda: A.nms(boxes, scores, thr), repeats)
+    kept = len(A.nms_device(boxes, scores, thr))
+    print(f"NMS alone, n = {n} (thr {thr}, {kept} kept): device {stats(t_dev)}")
+    print(f"  host sweep: {stats(t_host)}; host - device = {statistics.median(t_host) - statistics.median(t_dev):.2f} ms")
+
+
+if args.standalone:
+    min_area = args.min_area or 100
+    print(f"standalone: {args.masks} seeded blob masks of {args.height} x {args.width}, min_area {min_area}; {args.repeats} repeats after 1 warm-up")
+    bench_cleanup(blob_masks(args.masks, args.height, args.width, 72).to(dev), min_area, args.repeats)
+    for n_boxes in (300, 1000, 3072):
+        bench_nms(n_boxes, args.repeats)
+    sys.exit(0)
+
 cfg = SAM_CONFIGS[args.model]
 frames, _ = synthetic_clip(T=1, H=args.height, W=args.width, seed=72)
 img = frames[0].permute(1, 2, 0).contiguous().numpy()
 pred = SamPredictor(SamHip(config=cfg, seed=72, precision=args.precision, hq=args.hq).to(dev))
-sync = torch.cuda.synchronize
 
 # ---- set_image alone
 pred.set_image(img)
@@ -80,11 +173,56 @@ print(f"{len(ious)} candidates: |low-res logit| median {float(low.abs().median()
       f"({100.0 * passed.mean():.1f} %)")
 del low, iou, rec
 kw = dict(points_per_side=args.points_per_side, points_per_batch=nb, pred_iou_thresh=iou_thr, stability_score_thresh=stab_thr,
-          stability_score_offset=args.offset)
+          stability_score_offset=args.offset, min_mask_region_area=args.min_area)
+n_cand = len(ious)
+
+# ---- generate(), alternating, set_image timed inside and subtracted
+t_in_set = [0.0]
+orig_set = pred.set_image
+
+
+def timed_set_image(*a, **k):
+    sync()
+    t0 = time.perf_counter()
+    orig_set(*a, **k)
+    sync()
+    t_in_set[0] += time.perf_counter() - t0
+
+
+pred.set_image = timed_set_image
+if args.tail == "both":
+    # ---- the tail: device_tail=True against False on the fused path, alternating in one process
+    gens = {t: A.SamAutomaticMaskGenerator(None, predictor=pred, fused=True, device_tail=t, **kw) for t in (False, True)}
+    times = {t: [] for t in gens}
+    n_rec = {}
+    for r in range(args.warmup + args.repeats):
+        for t in (False, True):
+            t_in_set[0] = 0.0
+            sync()
+            t0 = time.perf_counter()
+            recs = gens[t].generate(img)
+            sync()
+            dt = (time.perf_counter() - t0 - t_in_set[0]) * 1e3
+            n_rec[t] = len(recs)
+            if r >= args.warmup:
+                times[t].append(dt)
+    for t in (True, False):
+        print(f"generate() min_area {args.min_area}, device_tail={t}: {stats(times[t])} over {len(times[t])} repeats; {n_rec[t]} records")
+    a, b = statistics.median(times[False]), statistics.median(times[True])
+    sp = [max(times[t]) - min(times[t]) for t in (False, True)]
+    print(f"host tail - device tail = {a - b:.1f} ms ({a / b:.2f} x); spreads {sp[0]:.1f} (host) + {sp[1]:.1f} (device) = {sum(sp):.1f} ms, "
+          f"the larger {max(sp):.1f} ms")
+    # ---- the two steps alone: the clean-up of the masks that reach it, NMS at the candidate count
+    g0 = A.SamAutomaticMaskGenerator(None, predictor=pred, fused=True, device_tail=True, **{**kw, "min_mask_region_area": 0})
+    survivors = g0._generate_masks(img)["masks"]
+    bench_cleanup(survivors, args.min_area or 100, args.repeats)
+    bench_nms(n_cand, args.repeats)
+    sys.exit(0)
+
 paths = {"both": [False, True], "fused": [True], "unfused": [False]}[args.only]
 if args.hq:
     paths = [True]                                     # fused=False with HQ-SAM decodes prompt by prompt: nothing batched to compare
-gens = {f: A.SamAutomaticMaskGenerator(None, predictor=pred, fused=f, **kw) for f in paths}
+gens = {f: A.SamAutomaticMaskGenerator(None, predictor=pred, fused=f, device_tail=args.tail == "device", **kw) for f in paths}
 
 if args.launches:
     from torch.profiler import ProfilerActivity, profile
@@ -108,20 +246,6 @@ if args.launches:
         print(f"fused={f}: one batch of {nb} points = {kern} kernel launches + {copies} copies / memsets")
     sys.exit(0)
 
-# ---- generate(), alternating, set_image timed inside and subtracted
-t_in_set = [0.0]
-orig_set = pred.set_image
-
-
-def timed_set_image(*a, **k):
-    sync()
-    t0 = time.perf_counter()
-    orig_set(*a, **k)
-    sync()
-    t_in_set[0] += time.perf_counter() - t0
-
-
-pred.set_image = timed_set_image
 times = {f: [] for f in paths}
 n_rec = {}
 for r in range(args.warmup + args.repeats):
