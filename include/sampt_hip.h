@@ -381,6 +381,33 @@ int sampt_amg_regions(const uint8_t* masks_in_dev, int n, int h, int w, int min_
 size_t sampt_amg_nms_workspace_bytes(int n);
 int sampt_amg_nms(const float* boxes_dev, const float* scores_dev, int n, float iou_thr, int64_t* keep_out_dev,
                   int32_t* count_out_dev, void* workspace_dev, size_t workspace_bytes, sampt_stream_t stream);
+/* COCO run-length encoding of a contiguous stack x_dev [n][h][w] on the device, h * w < 2^31: bytes (non-zero = set; is_f32 = 0)
+ * or f32 values with a threshold (is_f32 = 1: set iff x > thr; NaN and x == thr are clear).  Runs go over the column-major
+ * flattening p = x * h + y and the first run counts zeros (a mask whose first pixel is set starts with a 0 count): exactly
+ * mask_to_rle of sam_pt_amd/automatic_mask_generator.py.  All integer, no atomics: bitwise repeatable.  Between the phases the
+ * host reads one total.
+ * count: offsets_out_dev int64 [n + 1] = the number of runs of the masks before m ([n] = the stack's total, the length of the
+ *   counts array), area_out_dev int32 [n] = set pixels (the sum of the odd runs).  The pixels are read once, here; rows that are
+ *   4-byte (f32: 16-byte) aligned (w % 4 == 0 and an aligned x_dev) are read with one vector load per 4 pixels, others element by
+ *   element with the same result.  The workspace (16-byte aligned, sampt_rle_workspace_bytes(n, h, w) = 16 bytes per 64 pixels of
+ *   a column + 16 per mask; 0 for a bad shape) keeps the transition words for emit; with less the call fails with
+ *   SAMPT_ERR_WORKSPACE and the caller splits the stack by masks.
+ * emit: the same n, h, w, workspace and the offsets of count -> counts_out_dev uint32 [offsets[n]], mask m at [offsets[m], offsets[m + 1]).
+ * string_sizes / string_emit: the COCO string of every mask's counts (maskApi rleToString: c[i] - c[i - 2] for i > 2, 5 bits at a
+ *   time from the low end with an arithmetic shift, bit 5 = more to come, chr(chunk + 48)), concatenated.  sizes writes
+ *   str_offsets_dev [n] (int64 [n + 1]) = the total bytes; emit writes chars_out_dev uint8 [that total] and str_offsets_dev [0 .. n).
+ *   total_counts = offsets[n]; workspace (8-byte aligned) of sampt_rle_string_workspace_bytes(total_counts), the same for both. */
+size_t sampt_rle_workspace_bytes(int n, int h, int w);
+int sampt_rle_count(const void* x_dev, int is_f32, float thr, int n, int h, int w, int64_t* offsets_out_dev, int32_t* area_out_dev,
+                    void* workspace_dev, size_t workspace_bytes, sampt_stream_t stream);
+int sampt_rle_emit(int n, int h, int w, const int64_t* offsets_dev, uint32_t* counts_out_dev, const void* workspace_dev,
+                   size_t workspace_bytes, sampt_stream_t stream);
+size_t sampt_rle_string_workspace_bytes(int64_t total_counts);
+int sampt_rle_string_sizes(const uint32_t* counts_dev, const int64_t* offsets_dev, int n, int64_t total_counts,
+                           int64_t* str_offsets_dev, void* workspace_dev, size_t workspace_bytes, sampt_stream_t stream);
+int sampt_rle_string_emit(const uint32_t* counts_dev, const int64_t* offsets_dev, int n, int64_t total_counts,
+                          int64_t* str_offsets_dev, uint8_t* chars_out_dev, const void* workspace_dev, size_t workspace_bytes,
+                          sampt_stream_t stream);
 /* Whole SamPt.predict_mask chain (sam_pt.py:760-837) for `frames` independent (frame, object) items that share the
  * visible-point count k, batched into one launch sequence and without host synchronisation:
  * [positives-only pass over the first n_pos_first points when n_pos_first >= 0, i.e. negative_points_per_mask > 0;

@@ -14,7 +14,9 @@ constructor keywords and record format:
   preferring small crops -> optional small-region clean-up -> records.
 
 MI355X notes: upstream run-length encodes every surviving mask on the host to bound memory; with 288 GB of HBM the boolean
-masks simply stay on the device until the records are built (RLE helpers are kept for ``output_mode="uncompressed_rle"``).
+masks simply stay on the device until the records are built.  With the device tail the RLE output modes are encoded there too
+(``rle_encode_device``, csrc/rle.hip: one pass over the pixels, only the runs or their COCO strings reach the host;
+``output_mode="coco_rle"`` exists on that path only); the host ``mask_to_rle`` stays as the yardstick and the host path.
 Two paths through a batch of points, chosen by ``fused``:
 
   * fused (default with the HIP ``SamPredictor``): ``predict_points_batch`` decodes the whole batch as ONE decoder chain against
@@ -158,15 +160,65 @@ def mask_to_rle(masks: torch.Tensor) -> List[Dict[str, Any]]:
     return out
 
 
+def coco_rle_string(counts) -> str:
+    """The COCO string of uncompressed counts: maskApi.c ``rleToString``.  Count i > 2 is replaced by its difference to count
+    i - 2; the value is written 5 bits at a time from the low end (arithmetic shift: -1 stays -1); a chunk is the last when the
+    rest is 0 with bit 4 clear or -1 with bit 4 set, otherwise bit 5 is set; every chunk becomes ``chr(chunk + 48)``.
+    **Parity unpinned**: restated from the published algorithm, pycocotools is absent."""
+    counts = [int(c) for c in counts]
+    out = []
+    for i, c in enumerate(counts):
+        x = c - counts[i - 2] if i > 2 else c
+        while True:
+            chunk = x & 0x1f
+            x >>= 5                                              # Python's >> on a negative int is arithmetic
+            more = (x != -1) if chunk & 0x10 else (x != 0)
+            if more:
+                chunk |= 0x20
+            out.append(chr(chunk + 48))
+            if not more:
+                break
+    return "".join(out)
+
+
+def coco_rle_counts(s) -> List[int]:
+    """Inverse of ``coco_rle_string``: maskApi.c ``rleFrString`` (sign extension from the last chunk's bit 4, then the
+    difference to count i - 2 is undone for i > 2).  **Parity unpinned** against pycocotools, which is absent."""
+    if isinstance(s, (bytes, bytearray)):
+        s = s.decode("ascii")
+    counts: List[int] = []
+    p = 0
+    while p < len(s):
+        x, k, more = 0, 0, True
+        while more:
+            c = ord(s[p]) - 48
+            x |= (c & 0x1f) << (5 * k)
+            more = bool(c & 0x20)
+            p += 1
+            k += 1
+            if not more and (c & 0x10):
+                x |= -1 << (5 * k)
+        if len(counts) > 2:
+            x += counts[-2]
+        counts.append(x)
+    return counts
+
+
+def _rle_counts(rle: Dict[str, Any]):
+    c = rle["counts"]
+    return coco_rle_counts(c) if isinstance(c, (str, bytes, bytearray)) else c
+
+
 def rle_to_mask(rle: Dict[str, Any]) -> np.ndarray:
+    """Uncompressed (``counts`` a list) or compressed (``counts`` a COCO string) record -> bool (h, w)."""
     h, w = rle["size"]
-    counts = np.asarray(rle["counts"], dtype=np.int64)
+    counts = np.asarray(_rle_counts(rle), dtype=np.int64)
     values = (np.arange(len(counts)) % 2).astype(bool)
     return np.repeat(values, counts).reshape(w, h).T
 
 
 def area_from_rle(rle: Dict[str, Any]) -> int:
-    return int(sum(rle["counts"][1::2]))
+    return int(sum(_rle_counts(rle)[1::2]))
 
 
 # --------------------------------------------------------------------------------------------------------------------
@@ -284,6 +336,102 @@ def remove_small_regions_device(masks: torch.Tensor, min_area: float, workspace_
     return out, changed, area.to(torch.int64), boxes.to(torch.int64)
 
 
+_RLE_WS_CAP = 1 << 28              # workspace of one encoder call; a larger stack is encoded in chunks of masks
+
+
+def rle_encode_device(x: torch.Tensor, threshold: Optional[float] = None, compressed: bool = False,
+                      workspace_bytes: Optional[int] = None):
+    """``mask_to_rle`` on the HIP device (csrc/rle.hip).  ``x``: bool / uint8 (..., H, W) (non-zero = set), or a float tensor
+    with ``threshold`` (set iff ``x > threshold``; NaN and equality are clear) — the logits are then encoded without a boolean
+    copy.  Returns (records, areas): one ``{"size": [h, w], "counts": list[int]}`` per mask in row-major order of the leading
+    dimensions — ``"counts": str`` (``coco_rle_string``) when ``compressed`` — and the int64 areas on the device.  The pixels
+    are read once on the device; the host receives the runs (or the strings) and reads one total between the phases.
+    ``workspace_bytes`` bounds the scratch memory (default: the whole stack, at most 256 MiB); a stack that needs more is
+    encoded in chunks of masks, less than one mask's worth is an error."""
+    from . import _lib
+    _lib.require_hip(x.device, "rle_encode_device")
+    if x.dim() < 2:
+        raise _lib.SamptError(f"rle_encode_device: a (..., H, W) tensor is required; got {tuple(x.shape)}")
+    is_f32 = x.dtype.is_floating_point
+    if is_f32:
+        if threshold is None:
+            raise _lib.SamptError("rle_encode_device: a float tensor needs a threshold")
+        if x.dtype != torch.float32:
+            raise _lib.SamptError(f"rle_encode_device: float input must be float32; got {x.dtype}")
+    elif x.dtype not in (torch.bool, torch.uint8):
+        raise _lib.SamptError(f"rle_encode_device: bool, uint8 or float input is required; got {x.dtype}")
+    elif threshold is not None:
+        raise _lib.SamptError("rle_encode_device: threshold applies to float input only")
+    h, w = int(x.shape[-2]), int(x.shape[-1])
+    n = int(np.prod(x.shape[:-2], dtype=np.int64))
+    dev = x.device
+    if n == 0:
+        return [], torch.zeros(0, dtype=torch.int64, device=dev)
+    if h == 0 or w == 0:
+        raise _lib.SamptError(f"rle_encode_device: empty masks {tuple(x.shape)}")
+    lib = _lib.load()
+    per = int(lib.sampt_rle_workspace_bytes(1, h, w))
+    if per == 0:
+        raise _lib.SamptError(f"rle_encode_device: h * w must be below 2^31; got {h} x {w}")
+    if workspace_bytes is None:
+        workspace_bytes = max(per, min(n * per, _RLE_WS_CAP))
+    chunk = max(1, min(n, int(workspace_bytes) // per))          # (0 masks' worth: the call itself refuses the workspace)
+    records: List[Dict[str, Any]] = []
+    with _lib.device_guard(dev):
+        x = x.reshape(n, h, w)                                   # (a view when x is contiguous; slices of it keep their offset)
+        if not x.is_contiguous():
+            x = x.contiguous()
+        stream = _lib.stream_ptr()
+        ws = torch.empty(max(16, int(workspace_bytes)), dtype=torch.uint8, device=dev)
+        areas = torch.empty(n, dtype=torch.int32, device=dev)
+        for c0 in range(0, n, chunk):
+            c = min(chunk, n - c0)
+            xc = x[c0:c0 + c]
+            offsets = torch.empty(c + 1, dtype=torch.int64, device=dev)
+            _lib.check(lib.sampt_rle_count(_lib.ptr(xc), int(is_f32), float(threshold or 0.0), c, h, w, _lib.ptr(offsets),
+                                           _lib.c_void_p(areas.data_ptr() + 4 * c0), _lib.ptr(ws), int(workspace_bytes), stream),
+                       "sampt_rle_count")
+            total = int(offsets[c].item())                       # host read 1: the number of runs
+            counts = torch.empty(total, dtype=torch.int32, device=dev)      # (uint32 values below 2^31)
+            _lib.check(lib.sampt_rle_emit(c, h, w, _lib.ptr(offsets), _lib.ptr(counts), _lib.ptr(ws), int(workspace_bytes),
+                                          stream), "sampt_rle_emit")
+            if not compressed:
+                off = offsets.cpu().tolist()
+                flat = counts.cpu().numpy()
+                records += [{"size": [h, w], "counts": flat[off[i]:off[i + 1]].tolist()} for i in range(c)]
+                continue
+            sws = torch.empty(max(16, int(lib.sampt_rle_string_workspace_bytes(total))), dtype=torch.uint8, device=dev)
+            soff = torch.empty(c + 1, dtype=torch.int64, device=dev)
+            _lib.check(lib.sampt_rle_string_sizes(_lib.ptr(counts), _lib.ptr(offsets), c, total, _lib.ptr(soff), _lib.ptr(sws),
+                                                  sws.numel(), stream), "sampt_rle_string_sizes")
+            nbytes = int(soff[c].item())                         # host read 2: the number of characters
+            chars = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.sampt_rle_string_emit(_lib.ptr(counts), _lib.ptr(offsets), c, total, _lib.ptr(soff), _lib.ptr(chars),
+                                                 _lib.ptr(sws), sws.numel(), stream), "sampt_rle_string_emit")
+            off = soff.cpu().tolist()
+            text = chars.cpu().numpy().tobytes().decode("ascii")
+            records += [{"size": [h, w], "counts": text[off[i]:off[i + 1]]} for i in range(c)]
+    return records, areas.to(torch.int64)
+
+
+def encode_rle(x: torch.Tensor, threshold: Optional[float] = None, compressed: bool = False) -> List[Dict[str, Any]]:
+    """RLE records of a (..., H, W) stack wherever it lives: ``rle_encode_device`` for a HIP tensor, ``mask_to_rle``
+    (+ ``coco_rle_string``) for a CPU tensor.  A float stack is binarised as ``x > threshold``."""
+    if getattr(x.device, "type", None) == "cuda":
+        return rle_encode_device(x, threshold=threshold, compressed=compressed)[0]
+    if x.dtype.is_floating_point:
+        if threshold is None:
+            raise ValueError("encode_rle: a float tensor needs a threshold")
+        x = x > threshold
+    if x.numel() == 0:
+        return []
+    records = mask_to_rle(x.reshape((-1,) + tuple(x.shape[-2:])) != 0)
+    if compressed:
+        for r in records:
+            r["counts"] = coco_rle_string(r["counts"])
+    return records
+
+
 # --------------------------------------------------------------------------------------------------------------------
 class _MaskData:
     """Parallel per-mask columns (device tensors) that are filtered and concatenated together."""
@@ -334,8 +482,6 @@ class SamAutomaticMaskGenerator:
                 raise ValueError("point_grids needs one grid per crop layer (crop_n_layers + 1)")
         if output_mode not in ("binary_mask", "uncompressed_rle", "coco_rle"):
             raise ValueError(f"Unknown output_mode {output_mode}.")
-        if output_mode == "coco_rle":
-            raise NotImplementedError("output_mode='coco_rle' needs pycocotools, which this build does not ship")
         if isinstance(crop_overlap_ratio, str):                      # the shipped YAML spells it "512 / 1500"
             num, den = crop_overlap_ratio.split("/")
             crop_overlap_ratio = float(num) / float(den)
@@ -356,6 +502,9 @@ class SamAutomaticMaskGenerator:
             from . import _lib
             device_tail = on_hip and all(hasattr(_lib.load(), f) for f in ("sampt_amg_nms", "sampt_amg_regions"))
         self.device_tail = bool(device_tail)
+        if output_mode == "coco_rle" and not self.device_tail:
+            raise NotImplementedError("output_mode='coco_rle' is encoded by the device tail only (csrc/rle.hip); the host path "
+                                      "would need pycocotools, which this build does not ship")
         self.points_per_batch = points_per_batch
         self.pred_iou_thresh = pred_iou_thresh
         self.stability_score_thresh = stability_score_thresh
@@ -382,13 +531,18 @@ class SamAutomaticMaskGenerator:
         if self.min_mask_region_area > 0 and len(data):
             post = self._postprocess_small_regions_device if self.device_tail else self._postprocess_small_regions
             data = post(data, self.min_mask_region_area, max(self.box_nms_thresh, self.crop_nms_thresh))
-        masks = data["masks"].cpu() if len(data) else torch.zeros((0,) + tuple(image.shape[:2]), dtype=torch.bool)
         areas = data["area"].cpu().tolist() if self.device_tail else None          # (the host tail sums every mask below)
+        if self.device_tail and self.output_mode != "binary_mask":
+            # run-length encoded where the masks live: only the runs (or their strings) reach the host
+            masks = None
+            rles = rle_encode_device(data["masks"], compressed=self.output_mode == "coco_rle")[0] if len(data) else []
+        else:
+            masks = data["masks"].cpu() if len(data) else torch.zeros((0,) + tuple(image.shape[:2]), dtype=torch.bool)
+            rles = mask_to_rle(masks) if self.output_mode != "binary_mask" and len(masks) else None
         boxes, crops = data["boxes"].cpu(), data["crop_boxes"].cpu()
         ious, stab, pts = data["iou_preds"].cpu(), data["stability_score"].cpu(), data["points"].cpu()
-        rles = mask_to_rle(masks) if self.output_mode != "binary_mask" and len(masks) else None
         records = []
-        for i in range(masks.shape[0]):
+        for i in range(len(data)):
             records.append({
                 "segmentation": masks[i].numpy() if rles is None else rles[i],
                 "area": int(masks[i].sum()) if areas is None else int(areas[i]),

@@ -613,6 +613,51 @@ int sampt_amg_nms(const float* boxes, const float* scores, int n, float iou_thr,
   return rc == SAMPT_OK ? rc : fail(rc, "sampt_amg_nms: bad arguments (n outside 0..65535, null or misaligned pointer)");
 }
 
+size_t sampt_rle_workspace_bytes(int n, int h, int w) { return rle_workspace_bytes(n, h, w); }
+
+static int rle_bad_shape(const char* who, int n, int h, int w) {
+  if (n < 0 || h <= 0 || w <= 0) return fail(SAMPT_ERR_ARG, std::string(who) + ": bad shape");
+  if ((long)h * w >= (1L << 31)) return fail(SAMPT_ERR_ARG, std::string(who) + ": h * w must be below 2^31");
+  return SAMPT_OK;
+}
+
+int sampt_rle_count(const void* x, int is_f32, float thr, int n, int h, int w, int64_t* offsets_out, int32_t* area_out, void* ws,
+                    size_t ws_bytes, sampt_stream_t stream) {
+  if (rle_bad_shape("sampt_rle_count", n, h, w) != SAMPT_OK) return SAMPT_ERR_ARG;
+  int rc = rle_count(x, is_f32, thr, n, h, w, (long long*)offsets_out, (int*)area_out, ws, ws_bytes, (hipStream_t)stream);
+  if (rc == SAMPT_ERR_WORKSPACE) return fail(rc, "sampt_rle_count: workspace too small for n masks (split the stack by masks)");
+  if (rc == SAMPT_ERR_ARG) return fail(rc, "sampt_rle_count: null or misaligned pointer");
+  return rc;
+}
+
+int sampt_rle_emit(int n, int h, int w, const int64_t* offsets, uint32_t* counts_out, const void* ws, size_t ws_bytes,
+                   sampt_stream_t stream) {
+  if (rle_bad_shape("sampt_rle_emit", n, h, w) != SAMPT_OK) return SAMPT_ERR_ARG;
+  int rc = rle_emit(n, h, w, (const long long*)offsets, counts_out, ws, ws_bytes, (hipStream_t)stream);
+  if (rc == SAMPT_ERR_WORKSPACE) return fail(rc, "sampt_rle_emit: workspace smaller than the one sampt_rle_count filled");
+  if (rc == SAMPT_ERR_ARG) return fail(rc, "sampt_rle_emit: null or misaligned pointer");
+  return rc;
+}
+
+size_t sampt_rle_string_workspace_bytes(int64_t total_counts) { return rle_string_workspace_bytes((long)total_counts); }
+
+int sampt_rle_string_sizes(const uint32_t* counts, const int64_t* offsets, int n, int64_t total, int64_t* str_offsets, void* ws,
+                           size_t ws_bytes, sampt_stream_t stream) {
+  int rc = rle_string_sizes(counts, (const long long*)offsets, n, (long)total, (long long*)str_offsets, ws, ws_bytes, (hipStream_t)stream);
+  if (rc == SAMPT_ERR_WORKSPACE) return fail(rc, "sampt_rle_string_sizes: workspace too small");
+  if (rc == SAMPT_ERR_ARG) return fail(rc, "sampt_rle_string_sizes: bad arguments (n < 1, total_counts < n, null or misaligned pointer)");
+  return rc;
+}
+
+int sampt_rle_string_emit(const uint32_t* counts, const int64_t* offsets, int n, int64_t total, int64_t* str_offsets, uint8_t* chars_out,
+                          const void* ws, size_t ws_bytes, sampt_stream_t stream) {
+  int rc = rle_string_emit(counts, (const long long*)offsets, n, (long)total, (long long*)str_offsets, chars_out, ws, ws_bytes,
+                           (hipStream_t)stream);
+  if (rc == SAMPT_ERR_WORKSPACE) return fail(rc, "sampt_rle_string_emit: workspace too small");
+  if (rc == SAMPT_ERR_ARG) return fail(rc, "sampt_rle_string_emit: bad arguments (n < 1, total_counts < n, null or misaligned pointer)");
+  return rc;
+}
+
 int sampt_sam_track_decode(sampt_dec_t h, int frames, const float* features, const float* hq_features,
                            const float* pts, const int32_t* labels, int k, const int32_t* k_item,
                            const int32_t* npos_item, int ld_pts, int n_pos_first, int refine_iters, float iou_thr,

@@ -253,6 +253,20 @@ int amg_regions(const unsigned char* masks_in, int n, int h, int w, int min_area
 size_t amg_nms_workspace_bytes(int n);
 int amg_nms(const float* boxes, const float* scores, int n, float thr, long long* keep, int* count, void* ws, size_t ws_bytes,
             hipStream_t s);
+// ---- rle.hip: COCO run-length encoding of a stack [n][h][w] of bytes (non-zero = set) or of f32 values (set iff x > thr), exactly
+// mask_to_rle's runs (column-major, the first run counts zeros) and maskApi's rleToString of them.  h * w < 2^31.
+// count: offsets int64 [n + 1] (runs of the masks before m; [n] = the total the caller sizes `counts` by), area int32 [n]; it
+//   leaves the transition words in ws (rle_workspace_bytes(n, h, w), 16-byte aligned) for emit, which takes the same n, h, w, ws.
+// string_sizes: str_offsets[n] = characters of the whole stack; string_emit: the characters and str_offsets[0 .. n).
+size_t rle_workspace_bytes(int n, int h, int w);
+int rle_count(const void* x, int is_f32, float thr, int n, int h, int w, long long* offsets, int* area, void* ws, size_t ws_bytes,
+              hipStream_t s);
+int rle_emit(int n, int h, int w, const long long* offsets, unsigned* counts, const void* ws, size_t ws_bytes, hipStream_t s);
+size_t rle_string_workspace_bytes(long total);
+int rle_string_sizes(const unsigned* counts, const long long* offsets, int n, long total, long long* str_offsets, void* ws,
+                     size_t ws_bytes, hipStream_t s);
+int rle_string_emit(const unsigned* counts, const long long* offsets, int n, long total, long long* str_offsets, unsigned char* chars,
+                    const void* ws, size_t ws_bytes, hipStream_t s);
 int bbox_from_logits_state(const float* logits, int h, int w, int* bbox_state, int* bbox_partial, hipStream_t s);
 // mask-input embedding (PromptEncoder.mask_downscaling, App. A-4) fused with "src = image_embedding + dense":
 //   mask (4g x 4g) -> conv2x2s2(1->c1) LN2d GELU -> conv2x2s2(c1->c2) LN2d GELU -> conv1x1(c2->256) ; src = feat + dense

@@ -8,6 +8,11 @@ prompt + tensor work on full-resolution logits), alternating in one process.
                                                    # device_tail=True against False on the fused path, alternating, + the two steps alone
   python tools/amg_bench.py --standalone [--masks 100] [--min-area 100]   # the two steps alone on seeded inputs, no model: clean-up of
                                                    # blob masks (device call against the host loop), NMS at n = 300, 1000, 3072
+  python tools/amg_bench.py --standalone --rle [--masks 100] [--height 576] [--width 1024]   # run-length encoding alone on the
+                                                   # seeded blob masks: (a) masks.cpu() + mask_to_rle + coco_rle_string, the host
+                                                   # path, against (b) rle_encode_device(compressed=True); + the pixel pass's GB/s
+                                                   # for byte and for float input (hip events around sampt_rle_count)
+  python tools/amg_bench.py --output-mode coco_rle [...]   # generate() with an RLE output mode (coco_rle: device tail only)
   python tools/amg_bench.py --launches [...]      # kernel launches / copies of ONE batch of 64 points on either path (torch.profiler)
   rocprofv3 --kernel-trace --stats -d DIR -o amg -- python tools/amg_bench.py --only fused --repeats 1 --warmup 0
                                                    # then tools/rocprof_summary.py / tools/rocprof_by_grid.py on the .db
@@ -48,6 +53,9 @@ ap.add_argument("--tail", default="device", choices=["both", "device", "host"],
                 help="box NMS / clean-up on the device, on the host, or both alternating on the fused path")
 ap.add_argument("--standalone", action="store_true", help="time the clean-up and NMS alone on seeded inputs (no model)")
 ap.add_argument("--masks", type=int, default=100, help="--standalone: number of blob masks")
+ap.add_argument("--rle", action="store_true", help="--standalone: time the run-length encoding (host path against the device encoder)")
+ap.add_argument("--output-mode", default="binary_mask", choices=["binary_mask", "uncompressed_rle", "coco_rle"],
+                help="output_mode of generate()")
 args = ap.parse_args()
 
 dev = torch.device("cuda:0")
@@ -128,6 +136,83 @@ def bench_nms(n, repeats, thr=0.7, seed=5):
     print(f"  host sweep: {stats(t_host)}; host - device = {statistics.median(t_host) - statistics.median(t_dev):.2f} ms")
 
 
+def host_rle(masks):
+    """What the RLE output modes cost without the device encoder: every mask to the host, the numpy loop, the string codec."""
+    recs = A.mask_to_rle(masks.cpu())
+    for r in recs:
+        r["counts"] = A.coco_rle_string(r["counts"])
+    return recs
+
+
+def bench_rle_pixel_pass(x, threshold, repeats, what):
+    """sampt_rle_count alone (the pass over the pixels + the two small scans) between two events on the stream."""
+    from sam_pt_amd import _lib
+    lib = _lib.load()
+    n, h, w = x.shape
+    ws = torch.empty(lib.sampt_rle_workspace_bytes(n, h, w), dtype=torch.uint8, device=dev)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    area = torch.empty(n, dtype=torch.int32, device=dev)
+    is_f32 = int(x.dtype.is_floating_point)
+    t = []
+    for r in range(1 + repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        _lib.check(lib.sampt_rle_count(_lib.ptr(x), is_f32, float(threshold), n, h, w, _lib.ptr(offsets), _lib.ptr(area), _lib.ptr(ws),
+                                       ws.numel(), _lib.stream_ptr()), "sampt_rle_count")
+        e1.record()
+        sync()
+        if r >= 1:
+            t.append(e0.elapsed_time(e1))
+    nbytes = x.numel() * x.element_size()
+    gbs = nbytes / (statistics.median(t) * 1e-3) / 1e9
+    print(f"  pixel pass ({what}, {nbytes / 1e6:.1f} MB read once; words, scan and offsets included): {stats(t)} -> {gbs:.0f} GB/s of input "
+          f"= {100 * gbs / HBM_GBS:.1f} % of the {HBM_GBS:.0f} GB/s HBM peak")
+
+
+def bench_rle(masks, repeats):
+    n, h, w = masks.shape
+    exp = host_rle(masks)
+    got, _ = A.rle_encode_device(masks, compressed=True)
+    assert got == exp, "device and host encodings differ"
+    nruns = sum(len(A.coco_rle_counts(r["counts"])) for r in exp)
+    nchars = sum(len(r["counts"]) for r in exp)
+    print(f"RLE alone, {n} masks of {h} x {w}: {nruns} runs ({nruns // n} per mask), {nchars / 1e6:.2f} MB of COCO strings against "
+          f"{n * h * w / 1e6:.1f} MB of mask bytes; device == host records")
+    t_host, t_dev = [], []
+    import gc
+    for r in range(1 + repeats):                                     # alternating in one process
+        gc.collect()                                                 # (the millions of Python ints of the previous records)
+        a = timed(lambda: host_rle(masks), 1, warmup=0)
+        gc.collect()
+        b = timed(lambda: A.rle_encode_device(masks, compressed=True), 1, warmup=0)
+        if r >= 1:
+            t_host += a
+            t_dev += b
+    a, b = statistics.median(t_host), statistics.median(t_dev)
+    print(f"  (a) host: masks.cpu() + mask_to_rle + coco_rle_string: {stats(t_host)}")
+    print(f"  (b) device: rle_encode_device(compressed=True), strings on the host at the end: {stats(t_dev)}")
+    print(f"  (a) - (b) = {a - b:.1f} ms ({a / b:.1f} x); spread of (a)'s repeats {max(t_host) - min(t_host):.1f} ms, of (b)'s "
+          f"{max(t_dev) - min(t_dev):.1f} ms")
+    t_alone = timed(lambda: A.rle_encode_device(masks, compressed=True), repeats)
+    print(f"  (b) again, back to back (not alternating with the host path): {stats(t_alone)}")
+    bench_rle_pixel_pass(masks, 0.0, repeats, "bytes")
+    g = torch.Generator().manual_seed(73)
+    logits = (torch.randn(n, h // 8 + 2, w // 8 + 2, generator=g)).to(dev)
+    logits = torch.nn.functional.interpolate(logits[:, None], size=(h, w), mode="bilinear", align_corners=False)[:, 0].contiguous()
+    bench_rle_pixel_pass(logits, 0.0, repeats, "f32 logits, threshold 0")
+    # the stacks above fit the 256 MiB Infinity Cache, so a repeated pass can be served from it: the same pass over stacks that do not
+    reps_b, reps_f = -(-300_000_000 // masks.numel()), -(-75_000_000 // logits.numel())
+    bench_rle_pixel_pass(masks.repeat(reps_b, 1, 1), 0.0, repeats, f"bytes, the stack {reps_b} times over")
+    bench_rle_pixel_pass(logits.repeat(reps_f, 1, 1), 0.0, repeats, f"f32 logits, the stack {reps_f} times over")
+    t_f = timed(lambda: A.rle_encode_device(logits, threshold=0.0, compressed=True), repeats)
+    print(f"  rle_encode_device(f32 logits, threshold=0.0, compressed=True) end to end: {stats(t_f)}")
+
+
+if args.standalone and args.rle:
+    print(f"standalone RLE: {args.masks} seeded blob masks of {args.height} x {args.width}; {args.repeats} repeats after 1 warm-up")
+    bench_rle(blob_masks(args.masks, args.height, args.width, 72).to(dev), args.repeats)
+    sys.exit(0)
+
 if args.standalone:
     min_area = args.min_area or 100
     print(f"standalone: {args.masks} seeded blob masks of {args.height} x {args.width}, min_area {min_area}; {args.repeats} repeats after 1 warm-up")
@@ -173,7 +258,7 @@ print(f"{len(ious)} candidates: |low-res logit| median {float(low.abs().median()
       f"({100.0 * passed.mean():.1f} %)")
 del low, iou, rec
 kw = dict(points_per_side=args.points_per_side, points_per_batch=nb, pred_iou_thresh=iou_thr, stability_score_thresh=stab_thr,
-          stability_score_offset=args.offset, min_mask_region_area=args.min_area)
+          stability_score_offset=args.offset, min_mask_region_area=args.min_area, output_mode=args.output_mode)
 n_cand = len(ious)
 
 # ---- generate(), alternating, set_image timed inside and subtracted
