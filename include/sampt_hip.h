@@ -408,6 +408,26 @@ int sampt_rle_string_sizes(const uint32_t* counts_dev, const int64_t* offsets_de
 int sampt_rle_string_emit(const uint32_t* counts_dev, const int64_t* offsets_dev, int n, int64_t total_counts,
                           int64_t* str_offsets_dev, uint8_t* chars_out_dev, const void* workspace_dev, size_t workspace_bytes,
                           sampt_stream_t stream);
+/* DAVIS J and F on the device: six integer counts per item i of n, an item being a pair of binary images (h, w) — seg (the
+ * prediction) and ann (the ground truth):
+ *   counts_out_dev int32 [n][6] = inter |seg & ann|, union |seg | ann|, n_seg |B(seg)|, n_ann |B(ann)|,
+ *                                 seg_match |B(seg) & dil(B(ann))|, ann_match |B(ann) & dil(B(seg))|
+ * B = the boundary map of sam_pt_amd/vos_metrics.py seg2bmap, dil = binary dilation with the disk dy^2 + dx^2 <= radius^2
+ * (0 <= radius <= 64; the host derives it from bound_th), everything outside the image 0.  h * w < 2^31.
+ * An image is a plane of a contiguous stack [.][h][w]: kind 0 = bytes (set iff non-zero), kind 1 = f32 (set iff x > thr; NaN
+ * and x == thr are clear), kind 2 = a uint8 index map (set iff x == values_dev[i], int32 [n], required for this kind only).
+ * planes_dev int32 [n] names the plane of every item, so that several items share one plane (the objects of one frame of an index
+ * map); NULL: item i reads plane i.  The plane numbers are not checked on the device: the caller validates them.
+ * void_dev: optional bytes [.][h][w] with their own optional plane numbers; non-zero pixels are cleared from seg and ann first.
+ * Every pixel is read once, 4 pixels per load from any pixel address (rows of a width that is no multiple of 4 are not aligned;
+ * images narrower than 4 are read element by element, with the same result); the workspace (16-byte aligned, sampt_jf_workspace_bytes = 2 bits per pixel rounded up to 64 rows; 0 for
+ * a bad shape or radius) holds the two boundary bit-planes, the dilated maps are never written.  Integer sums: bitwise repeatable.
+ * With too small a workspace the call fails with SAMPT_ERR_WORKSPACE and the caller splits the stack by items. */
+size_t sampt_jf_workspace_bytes(int n, int h, int w, int radius);
+int sampt_jf_counts(const void* seg_dev, int seg_kind, float seg_thr, const int32_t* seg_values_dev, const int32_t* seg_planes_dev,
+                    const void* ann_dev, int ann_kind, float ann_thr, const int32_t* ann_values_dev, const int32_t* ann_planes_dev,
+                    const uint8_t* void_dev, const int32_t* void_planes_dev, int n, int h, int w, int radius,
+                    int32_t* counts_out_dev, void* workspace_dev, size_t workspace_bytes, sampt_stream_t stream);
 /* Whole SamPt.predict_mask chain (sam_pt.py:760-837) for `frames` independent (frame, object) items that share the
  * visible-point count k, batched into one launch sequence and without host synchronisation:
  * [positives-only pass over the first n_pos_first points when n_pos_first >= 0, i.e. negative_points_per_mask > 0;

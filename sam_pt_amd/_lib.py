@@ -89,6 +89,9 @@ _SIGS = {
     "sampt_rle_string_workspace_bytes": (c_size_t, [C.c_int64]),
     "sampt_rle_string_sizes": (c_int, [_P, _P, c_int, C.c_int64, _P, _P, c_size_t, _P]),
     "sampt_rle_string_emit": (c_int, [_P, _P, c_int, C.c_int64, _P, _P, _P, c_size_t, _P]),
+    "sampt_jf_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "sampt_jf_counts": (c_int, [_P, c_int, c_float, _P, _P, _P, c_int, c_float, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P,
+                                c_size_t, _P]),
     "sampt_sam_track_decode": (c_int, [_P, c_int, _P, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_float, c_int, c_int, c_int,
                                        c_int, _P, _P, _P, c_size_t, _P]),
     "sampt_sam_track_decode_graph": (c_int, [_P, c_int, _P, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_float, c_int, c_int,

@@ -658,6 +658,25 @@ int sampt_rle_string_emit(const uint32_t* counts, const int64_t* offsets, int n,
   return rc;
 }
 
+size_t sampt_jf_workspace_bytes(int n, int h, int w, int radius) { return jf_workspace_bytes(n, h, w, radius); }
+
+int sampt_jf_counts(const void* seg, int seg_kind, float seg_thr, const int32_t* seg_values, const int32_t* seg_planes, const void* ann,
+                    int ann_kind, float ann_thr, const int32_t* ann_values, const int32_t* ann_planes, const uint8_t* void_px,
+                    const int32_t* void_planes, int n, int h, int w, int radius, int32_t* counts_out, void* ws, size_t ws_bytes,
+                    sampt_stream_t stream) {
+  if (n <= 0 || h <= 0 || w <= 0) return fail(SAMPT_ERR_ARG, "sampt_jf_counts: bad shape (n, h and w must be positive)");
+  if ((long)h * w >= (1L << 31)) return fail(SAMPT_ERR_ARG, "sampt_jf_counts: h * w must be below 2^31");
+  if (radius < 0 || radius > 64) return fail(SAMPT_ERR_ARG, "sampt_jf_counts: radius must be in 0 .. 64");
+  if (seg_kind < 0 || seg_kind > 2 || ann_kind < 0 || ann_kind > 2)
+    return fail(SAMPT_ERR_ARG, "sampt_jf_counts: unknown kind (0 = bytes, 1 = f32 with a threshold, 2 = uint8 index map)");
+  int rc = jf_counts(seg, seg_kind, seg_thr, (const int*)seg_values, (const int*)seg_planes, ann, ann_kind, ann_thr, (const int*)ann_values,
+                     (const int*)ann_planes, void_px, (const int*)void_planes, n, h, w, radius, (int*)counts_out, ws, ws_bytes,
+                     (hipStream_t)stream);
+  if (rc == SAMPT_ERR_WORKSPACE) return fail(rc, "sampt_jf_counts: workspace too small for n items (split the stack by items)");
+  if (rc == SAMPT_ERR_ARG) return fail(rc, "sampt_jf_counts: null or misaligned pointer (an index map needs its values)");
+  return rc;
+}
+
 int sampt_sam_track_decode(sampt_dec_t h, int frames, const float* features, const float* hq_features,
                            const float* pts, const int32_t* labels, int k, const int32_t* k_item,
                            const int32_t* npos_item, int ld_pts, int n_pos_first, int refine_iters, float iou_thr,

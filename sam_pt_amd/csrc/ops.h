@@ -267,6 +267,14 @@ int rle_string_sizes(const unsigned* counts, const long long* offsets, int n, lo
                      size_t ws_bytes, hipStream_t s);
 int rle_string_emit(const unsigned* counts, const long long* offsets, int n, long total, long long* str_offsets, unsigned char* chars,
                     const void* ws, size_t ws_bytes, hipStream_t s);
+// ---- vos_metrics.hip: the six integer counts of DAVIS J and F per item (inter, union, n_seg, n_ann, seg_match, ann_match) of two
+// stacks of planes [.][h][w]; kind 0 = bytes (non-zero), 1 = f32 (x > thr), 2 = uint8 index map (x == values[i]); planes (or
+// null: item i reads plane i) and values are int32 [n] on the device.  void_px: optional byte planes cleared from both images.
+// 0 <= radius <= 64, h * w < 2^31; counts int32 [n][6]; ws of jf_workspace_bytes (16-byte aligned) holds the boundary bit-planes.
+size_t jf_workspace_bytes(int n, int h, int w, int radius);
+int jf_counts(const void* seg, int seg_kind, float seg_thr, const int* seg_values, const int* seg_planes, const void* ann, int ann_kind,
+              float ann_thr, const int* ann_values, const int* ann_planes, const unsigned char* void_px, const int* void_planes, int n,
+              int h, int w, int radius, int* counts, void* ws, size_t ws_bytes, hipStream_t s);
 int bbox_from_logits_state(const float* logits, int h, int w, int* bbox_state, int* bbox_partial, hipStream_t s);
 // mask-input embedding (PromptEncoder.mask_downscaling, App. A-4) fused with "src = image_embedding + dense":
 //   mask (4g x 4g) -> conv2x2s2(1->c1) LN2d GELU -> conv2x2s2(c1->c2) LN2d GELU -> conv1x1(c2->256) ; src = feat + dense
