@@ -428,6 +428,50 @@ int sampt_jf_counts(const void* seg_dev, int seg_kind, float seg_thr, const int3
                     const void* ann_dev, int ann_kind, float ann_thr, const int32_t* ann_values_dev, const int32_t* ann_planes_dev,
                     const uint8_t* void_dev, const int32_t* void_planes_dev, int n, int h, int w, int radius,
                     int32_t* counts_out_dev, void* workspace_dev, size_t workspace_bytes, sampt_stream_t stream);
+/* YouTube-VIS AP / AR on the device (csrc/vis_eval.hip): bit-planes of mask stacks, spatio-temporal intersection / union of all
+ * (detection, ground truth) pairs of a video, and the greedy matching of the reference's YTVOSeval.evaluateVid.  Integer work and
+ * one IEEE float64 division per IoU: bitwise repeatable and equal to the host restatement of sam_pt_amd/vis_metrics.py.
+ * Bit-plane format: a stack [n][h][w] is uint64 [n][ceil(h / 64)][w]; bit j of word (band b, column x) is pixel (64 b + j, x), and the
+ *   bits of rows >= h are 0 (every popcount below relies on it).  h * w < 2^31.
+ * bits_pack: x_dev is a contiguous stack [.][h][w] of kind 0 = bytes (set iff non-zero), kind 1 = f32 (set iff x > thr; NaN and
+ *   x == thr are clear) or kind 2 = a uint8 index map (set iff x == values_dev[i], int32 [n], this kind only).  planes_dev int32 [n]
+ *   names the plane of every item (NULL: item i reads plane i; not checked on the device).  bits_out_dev (16-byte aligned) receives the
+ *   n bit-planes, area_out_dev int32 [n] the set pixels.  Every pixel is read once, 4 pixels per load from any pixel address (images
+ *   narrower than 4: element by element, with the same result).  n = 0 is a no-op.
+ * rle_decode_bits: the inverse of sampt_rle_count / sampt_rle_emit.  counts_dev uint32 [total_counts] and offsets_dev int64 [n + 1]
+ *   hold column-major runs, the first run of a mask counting zeros; zero-length runs are legal.  status_out_dev int32 [n]: 0 = decoded;
+ *   1 = the runs do not sum to h * w; 2 = the mask's offsets are not ordered inside [0, total_counts].  A mask with a non-zero status
+ *   gets an all-zero plane and area 0, and nothing is read or written out of bounds for it.  The workspace (8-byte aligned,
+ *   sampt_rle_decode_workspace_bytes(total_counts) = 8 bytes per run + 16) holds the prefix sums of the runs.
+ * bits_unpack: n bit-planes -> bytes_out_dev [n][h][w] (0 / 1).
+ * seq_iou_counts: dt_planes_dev int32 [n_dt][n_frames] and gt_planes_dev int32 [n_gt][n_frames] name the bit-plane (of dt_bits_dev /
+ *   gt_bits_dev, with their areas int32 per plane) of every item on every frame; -1 (or a number >= the plane count given) means "no
+ *   mask on this frame"; several entries may name one plane.  counts_out_dev int64 [n_dt][n_gt][2] = inter = sum_t popc(d_t & g_t) and
+ *   union = sum_t (|d_t| + |g_t|) - inter, an absent frame contributing nothing of its own: an absent and an empty mask behave alike,
+ *   as in the reference's iou_seq.  The workspace (8-byte aligned, sampt_seq_iou_workspace_bytes; 0 for a bad shape) holds partial
+ *   sums that are added in a fixed order: no atomics.
+ * vis_match: one (video, category) group.  counts_dev as above with the detections in score order, cut to the last maxDets.  Per area
+ *   range a of n_ranges: gt_order_dev int32 [n_ranges][n_gt] (the stable sort of the ground truths by their ignore flag),
+ *   gt_ignore_dev bytes [n_ranges][n_gt] in that order, dt_out_dev bytes [n_ranges][n_dt] (the detection's average area is outside the
+ *   range); iscrowd_dev bytes [n_gt] in the original order; thrs_dev float64 [n_thr], n_thr <= 64; n_gt <= 960.  IoU = (double) inter /
+ *   (double) union, 0 for an empty union.  Outputs per (range, threshold): dt_match_out_dev int32 [n_ranges][n_thr][n_dt] = 1 + the
+ *   matched ground truth's original index, or 0; gt_match_out_dev int32 [n_ranges][n_thr][n_gt] = 1 + the matching detection's
+ *   position, or 0, in the range's order; dt_ignore_out_dev bytes [n_ranges][n_thr][n_dt]. */
+int sampt_bits_pack(const void* x_dev, int kind, float thr, const int32_t* values_dev, const int32_t* planes_dev, int n, int h, int w,
+                    uint64_t* bits_out_dev, int32_t* area_out_dev, sampt_stream_t stream);
+size_t sampt_rle_decode_workspace_bytes(int64_t total_counts);
+int sampt_rle_decode_bits(const uint32_t* counts_dev, const int64_t* offsets_dev, int n, int64_t total_counts, int h, int w,
+                          uint64_t* bits_out_dev, int32_t* area_out_dev, int32_t* status_out_dev, void* workspace_dev,
+                          size_t workspace_bytes, sampt_stream_t stream);
+int sampt_bits_unpack(const uint64_t* bits_dev, int n, int h, int w, uint8_t* bytes_out_dev, sampt_stream_t stream);
+size_t sampt_seq_iou_workspace_bytes(int n_dt, int n_gt, int n_frames, int h, int w);
+int sampt_seq_iou_counts(const uint64_t* dt_bits_dev, const int32_t* dt_area_dev, const int32_t* dt_planes_dev, int n_dt, int dt_n_planes,
+                         const uint64_t* gt_bits_dev, const int32_t* gt_area_dev, const int32_t* gt_planes_dev, int n_gt, int gt_n_planes,
+                         int n_frames, int h, int w, int64_t* counts_out_dev, void* workspace_dev, size_t workspace_bytes,
+                         sampt_stream_t stream);
+int sampt_vis_match(const int64_t* counts_dev, int n_dt, int n_gt, int n_ranges, int n_thr, const double* thrs_dev,
+                    const int32_t* gt_order_dev, const uint8_t* gt_ignore_dev, const uint8_t* iscrowd_dev, const uint8_t* dt_out_dev,
+                    int32_t* dt_match_out_dev, int32_t* gt_match_out_dev, uint8_t* dt_ignore_out_dev, sampt_stream_t stream);
 /* Whole SamPt.predict_mask chain (sam_pt.py:760-837) for `frames` independent (frame, object) items that share the
  * visible-point count k, batched into one launch sequence and without host synchronisation:
  * [positives-only pass over the first n_pos_first points when n_pos_first >= 0, i.e. negative_points_per_mask > 0;

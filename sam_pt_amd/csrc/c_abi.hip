@@ -658,6 +658,69 @@ int sampt_rle_string_emit(const uint32_t* counts, const int64_t* offsets, int n,
   return rc;
 }
 
+static int ve_bad_shape(const char* who, int n, int h, int w) {
+  if (n < 0 || h <= 0 || w <= 0) return fail(SAMPT_ERR_ARG, std::string(who) + ": bad shape");
+  if ((long)h * w >= (1L << 31)) return fail(SAMPT_ERR_ARG, std::string(who) + ": h * w must be below 2^31");
+  return SAMPT_OK;
+}
+
+int sampt_bits_pack(const void* x, int kind, float thr, const int32_t* values, const int32_t* planes, int n, int h, int w, uint64_t* bits_out,
+                    int32_t* area_out, sampt_stream_t stream) {
+  if (ve_bad_shape("sampt_bits_pack", n, h, w) != SAMPT_OK) return SAMPT_ERR_ARG;
+  if (kind < 0 || kind > 2) return fail(SAMPT_ERR_ARG, "sampt_bits_pack: unknown kind (0 = bytes, 1 = f32 with a threshold, 2 = uint8 index map)");
+  int rc = bits_pack(x, kind, thr, (const int*)values, (const int*)planes, n, h, w, (unsigned long long*)bits_out, (int*)area_out,
+                     (hipStream_t)stream);
+  if (rc == SAMPT_ERR_ARG) return fail(rc, "sampt_bits_pack: null or misaligned pointer (an index map needs its values)");
+  return rc;
+}
+
+size_t sampt_rle_decode_workspace_bytes(int64_t total_counts) { return rle_decode_workspace_bytes((long)total_counts); }
+
+int sampt_rle_decode_bits(const uint32_t* counts, const int64_t* offsets, int n, int64_t total, int h, int w, uint64_t* bits_out,
+                          int32_t* area_out, int32_t* status_out, void* ws, size_t ws_bytes, sampt_stream_t stream) {
+  if (ve_bad_shape("sampt_rle_decode_bits", n, h, w) != SAMPT_OK) return SAMPT_ERR_ARG;
+  if (total < 0) return fail(SAMPT_ERR_ARG, "sampt_rle_decode_bits: negative total_counts");
+  int rc = rle_decode_bits(counts, (const long long*)offsets, n, (long)total, h, w, (unsigned long long*)bits_out, (int*)area_out,
+                           (int*)status_out, ws, ws_bytes, (hipStream_t)stream);
+  if (rc == SAMPT_ERR_WORKSPACE) return fail(rc, "sampt_rle_decode_bits: workspace smaller than sampt_rle_decode_workspace_bytes(total_counts)");
+  if (rc == SAMPT_ERR_ARG) return fail(rc, "sampt_rle_decode_bits: null or misaligned pointer");
+  return rc;
+}
+
+int sampt_bits_unpack(const uint64_t* bits, int n, int h, int w, uint8_t* bytes_out, sampt_stream_t stream) {
+  if (ve_bad_shape("sampt_bits_unpack", n, h, w) != SAMPT_OK) return SAMPT_ERR_ARG;
+  int rc = bits_unpack((const unsigned long long*)bits, n, h, w, bytes_out, (hipStream_t)stream);
+  if (rc == SAMPT_ERR_ARG) return fail(rc, "sampt_bits_unpack: null or misaligned pointer");
+  return rc;
+}
+
+size_t sampt_seq_iou_workspace_bytes(int n_dt, int n_gt, int n_frames, int h, int w) {
+  return seq_iou_workspace_bytes(n_dt, n_gt, n_frames, h, w);
+}
+
+int sampt_seq_iou_counts(const uint64_t* dt_bits, const int32_t* dt_area, const int32_t* dt_planes, int n_dt, int dt_n_planes,
+                         const uint64_t* gt_bits, const int32_t* gt_area, const int32_t* gt_planes, int n_gt, int gt_n_planes, int n_frames,
+                         int h, int w, int64_t* counts_out, void* ws, size_t ws_bytes, sampt_stream_t stream) {
+  if (n_dt <= 0 || n_gt <= 0 || n_frames <= 0) return fail(SAMPT_ERR_ARG, "sampt_seq_iou_counts: n_dt, n_gt and n_frames must be positive");
+  if (ve_bad_shape("sampt_seq_iou_counts", 1, h, w) != SAMPT_OK) return SAMPT_ERR_ARG;
+  int rc = seq_iou_counts((const unsigned long long*)dt_bits, (const int*)dt_area, (const int*)dt_planes, n_dt, dt_n_planes,
+                          (const unsigned long long*)gt_bits, (const int*)gt_area, (const int*)gt_planes, n_gt, gt_n_planes, n_frames, h, w,
+                          (long long*)counts_out, ws, ws_bytes, (hipStream_t)stream);
+  if (rc == SAMPT_ERR_WORKSPACE) return fail(rc, "sampt_seq_iou_counts: workspace smaller than sampt_seq_iou_workspace_bytes");
+  if (rc == SAMPT_ERR_ARG) return fail(rc, "sampt_seq_iou_counts: bad arguments (too many items, negative plane count, null or misaligned pointer)");
+  return rc;
+}
+
+int sampt_vis_match(const int64_t* counts, int n_dt, int n_gt, int n_ranges, int n_thr, const double* thrs, const int32_t* gt_order,
+                    const uint8_t* gt_ignore, const uint8_t* iscrowd, const uint8_t* dt_out, int32_t* dt_match_out, int32_t* gt_match_out,
+                    uint8_t* dt_ignore_out, sampt_stream_t stream) {
+  int rc = vis_match((const long long*)counts, n_dt, n_gt, n_ranges, n_thr, thrs, (const int*)gt_order, gt_ignore, iscrowd, dt_out,
+                     (int*)dt_match_out, (int*)gt_match_out, dt_ignore_out, (hipStream_t)stream);
+  if (rc == SAMPT_ERR_ARG)
+    return fail(rc, "sampt_vis_match: bad arguments (n_dt >= 1, 1 <= n_gt <= 960, 1 <= n_thr <= 64, n_ranges >= 1, null or misaligned pointer)");
+  return rc;
+}
+
 size_t sampt_jf_workspace_bytes(int n, int h, int w, int radius) { return jf_workspace_bytes(n, h, w, radius); }
 
 int sampt_jf_counts(const void* seg, int seg_kind, float seg_thr, const int32_t* seg_values, const int32_t* seg_planes, const void* ann,

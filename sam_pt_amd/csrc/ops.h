@@ -275,6 +275,22 @@ size_t jf_workspace_bytes(int n, int h, int w, int radius);
 int jf_counts(const void* seg, int seg_kind, float seg_thr, const int* seg_values, const int* seg_planes, const void* ann, int ann_kind,
               float ann_thr, const int* ann_values, const int* ann_planes, const unsigned char* void_px, const int* void_planes, int n,
               int h, int w, int radius, int* counts, void* ws, size_t ws_bytes, hipStream_t s);
+// ---- vis_eval.hip: YouTube-VIS AP / AR.  Bit-planes: a stack [n][h][w] as uint64 [n][ceil(h / 64)][w], bit j of word (band b, column x)
+// = pixel (64 b + j, x), bits of rows >= h are 0.  pack: the three kinds of jf_counts -> bit-planes + area int32 [n].  rle_decode_bits:
+// the inverse of rle_count / rle_emit (status 0 = good; a bad mask's plane is zeros).  seq_iou_counts: int64 [D][G][2] = (inter, union)
+// over the frames, plane -1 = no mask on that frame.  vis_match: the greedy matching of evaluateVid per (area range, IoU threshold).
+int bits_pack(const void* x, int kind, float thr, const int* values, const int* planes, int n, int h, int w, unsigned long long* bits,
+              int* area, hipStream_t s);
+size_t rle_decode_workspace_bytes(long total);
+int rle_decode_bits(const unsigned* counts, const long long* offsets, int n, long total, int h, int w, unsigned long long* bits, int* area,
+                    int* status, void* ws, size_t ws_bytes, hipStream_t s);
+int bits_unpack(const unsigned long long* bits, int n, int h, int w, unsigned char* out, hipStream_t s);
+size_t seq_iou_workspace_bytes(int D, int G, int T, int h, int w);
+int seq_iou_counts(const unsigned long long* dt_bits, const int* dt_area, const int* dt_planes, int D, int dt_n_planes,
+                   const unsigned long long* gt_bits, const int* gt_area, const int* gt_planes, int G, int gt_n_planes, int T, int h, int w,
+                   long long* counts, void* ws, size_t ws_bytes, hipStream_t s);
+int vis_match(const long long* counts, int D, int G, int A, int n_thr, const double* thrs, const int* gt_order, const unsigned char* gt_ignore,
+              const unsigned char* iscrowd, const unsigned char* dt_out, int* dt_match, int* gt_match, unsigned char* dt_ignore, hipStream_t s);
 int bbox_from_logits_state(const float* logits, int h, int w, int* bbox_state, int* bbox_partial, hipStream_t s);
 // mask-input embedding (PromptEncoder.mask_downscaling, App. A-4) fused with "src = image_embedding + dense":
 //   mask (4g x 4g) -> conv2x2s2(1->c1) LN2d GELU -> conv2x2s2(c1->c2) LN2d GELU -> conv1x1(c2->256) ; src = feat + dense
