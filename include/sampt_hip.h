@@ -32,6 +32,7 @@ typedef void* sampt_stream_t; /* hipStream_t */
 typedef struct sampt_pips* sampt_pips_t;
 typedef struct sampt_pips2* sampt_pips2_t;
 typedef struct sampt_cotracker* sampt_cotracker_t;
+typedef struct sampt_raft* sampt_raft_t;
 typedef struct sampt_vit* sampt_vit_t;
 typedef struct sampt_dec* sampt_dec_t;
 
@@ -149,6 +150,43 @@ int sampt_cotracker_track_f32(sampt_cotracker_t h, const float* const pyr_dev[4]
                               const int32_t* query_t_dev, const float* query_xy_dev, const float* pos_x_dev,
                               const float* pos_y_dev, int iters, float* traj_out_dev, float* vis_out_dev,
                               void* workspace_dev, size_t workspace_bytes, sampt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * seam 1d — RAFT point tracker (sam_pt/point_tracker/raft/{tracker.py:29-88, raftnet.py:29-43, raft_core/}).
+ * Weights keyed by the names of raft-things.pth without "module." after sam_pt_amd.pack.pack_raft: convolutions
+ * [Cout][KH][KW][Cin] (both stems' Cin zero-padded 3 -> 4), cnet's eval-mode BatchNorms folded into the convolution in
+ * front of them, "update_block.encoder.convc1" K-padded 324 -> 352, "update_block.encoder.convf1.weight" as [98][128],
+ * "update_block.gru.convzr{1,2}" = [convz; convr], "update_block.flow_head.conv2" N-padded 2 -> 4.
+ *   flows_f32 : frames_dev uint8 (T,3,H,W) -> flows_fwd_dev / flows_bwd_dev [T-1][2][H][W] = Raftnet.forward(rgb[t],
+ *               rgb[t+1], iters)[0] and its reverse, un-padded; flow_low_dev (optional) [2][T-1][2][Hp/8][Wp/8] = the 1/8
+ *               resolution flows (forward stack, then backward).  fnet and cnet run once per frame; pair-directions go
+ *               through the correlation pyramid and the update block in chunks of as many pairs as the workspace holds
+ *               (workspace_bytes sizes it for max_pairs_in_flight; a smaller workspace means more chunks, same result).
+ *               Frames whose size padded to multiples of 8 is below 128 on either side are refused with
+ *               SAMPT_ERR_UNSUPPORTED: the coarsest correlation level would be a single cell, where the reference
+ *               divides by zero and returns NaN.
+ *   chain     : tracker.py:46-88 — query_points_dev [n][3] = (t, x, y); traj_out_dev [T][n][2] f32, vis_out_dev [T][n]
+ *               bytes (0 / 1).
+ * Test entry points: corr_pyramid (fmap1, fmap2 [hw][256] NHWC -> the 4 levels [hw][h_l w_l]; ws of
+ * sampt_raft_corr_pyramid_workspace_bytes), lookup (levels [M][h_l w_l] = one plane per row, coords [M][2] -> [M][352], any M >= 1),
+ * upsample (flow_low [P][h8][w8][2],
+ * mask [P][h8][w8][576] -> [P][2][H][W]).
+ * --------------------------------------------------------------------------------------------------------- */
+int sampt_raft_create(const char* const* names, const void* const* ptrs, int n, sampt_raft_t* out);
+void sampt_raft_destroy(sampt_raft_t h);
+int sampt_raft_workspace_bytes(sampt_raft_t h, int T, int H, int W, int max_pairs_in_flight, size_t* bytes);
+int sampt_raft_flows_f32(sampt_raft_t h, const uint8_t* frames_dev, int T, int H, int W, int iters, float* flows_fwd_dev,
+                         float* flows_bwd_dev, float* flow_low_dev, void* workspace_dev, size_t workspace_bytes,
+                         sampt_stream_t stream);
+int sampt_raft_chain(const float* flows_fwd_dev, const float* flows_bwd_dev, int T, int H, int W,
+                     const float* query_points_dev, int n, float* traj_out_dev, uint8_t* vis_out_dev, sampt_stream_t stream);
+size_t sampt_raft_corr_pyramid_workspace_bytes(int h8, int w8);
+int sampt_raft_corr_pyramid(const float* fmap1_dev, const float* fmap2_dev, int h8, int w8, float* const levels_dev[4],
+                            void* workspace_dev, size_t workspace_bytes, sampt_stream_t stream);
+int sampt_raft_lookup(const float* const levels_dev[4], int h8, int w8, const float* coords_dev, long m, float* out_dev,
+                      sampt_stream_t stream);
+int sampt_raft_upsample(const float* flow_low_dev, const float* mask_dev, float mask_scale, int pairs, int h8, int w8, int H,
+                        int W, float* out_dev, sampt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * seam 2a — SAM image encoder = SamPredictor.set_image (Sam.preprocess + ImageEncoderViT, Appendix A-1..A-3).

@@ -45,6 +45,15 @@ _SIGS = {
     "sampt_pips2_update_workspace_bytes": (c_int, [_P, c_int, c_int, C.POINTER(c_size_t)]),
     "sampt_pips2_update_f32": (c_int, [_P, C.POINTER(_P), c_int, c_int, _P, c_int, c_int, _P, c_int, C.POINTER(_P), c_int, _P,
                                        _P, c_size_t, _P]),
+    "sampt_raft_create": (c_int, [C.POINTER(c_char_p), C.POINTER(_P), c_int, C.POINTER(_P)]),
+    "sampt_raft_destroy": (None, [_P]),
+    "sampt_raft_workspace_bytes": (c_int, [_P, c_int, c_int, c_int, c_int, C.POINTER(c_size_t)]),
+    "sampt_raft_flows_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "sampt_raft_chain": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_int, _P, _P, _P]),
+    "sampt_raft_corr_pyramid_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "sampt_raft_corr_pyramid": (c_int, [_P, _P, c_int, c_int, C.POINTER(_P), _P, c_size_t, _P]),
+    "sampt_raft_lookup": (c_int, [C.POINTER(_P), c_int, c_int, _P, C.c_long, _P, _P]),
+    "sampt_raft_upsample": (c_int, [_P, _P, c_float, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "sampt_cotracker_create": (c_int, [C.POINTER(c_char_p), C.POINTER(_P), c_int, c_int, c_int, C.POINTER(_P)]),
     "sampt_cotracker_destroy": (None, [_P]),
     "sampt_resize_frames_f32": (c_int, [_P, c_int, C.c_long, c_int, c_int, _P, c_int, c_int, _P]),

@@ -55,6 +55,7 @@ struct sampt_pips {
 };
 struct sampt_pips2 { Pips2Engine e; };
 struct sampt_cotracker { CotEngine e; };
+struct sampt_raft { RaftEngine e; };
 struct sampt_vit { VitEngine e; };
 // hipGraph cache of the per-(frame, object) decode chain (north_star: "hipGraph capture of the per-frame decode"): one
 // instantiated graph per distinct call signature (every scalar AND every pointer of sampt_sam_track_decode_graph).
@@ -468,6 +469,96 @@ int sampt_pips2_update_f32(sampt_pips2_t h, const float* const pyr[4], int H0, i
   Arena a(ws, ws_bytes);
   return h->e.update(make_pyr(pyr, H0, W0), (const int*)frame_idx, n, S, trajs0, have_feat_init, feats, iters, trajs_out,
                      a, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------- RAFT
+static int raft_bad_size(const char* who, int H, int W) {
+  const int Hp = (H + 7) / 8 * 8, Wp = (W + 7) / 8 * 8;
+  if (Hp >= 128 && Wp >= 128) return SAMPT_OK;
+  return fail(SAMPT_ERR_UNSUPPORTED, std::string(who) + ": RAFT needs frames of at least 128 pixels on both sides after padding to "
+              "multiples of 8 (the coarsest of the 4 correlation levels must keep 2 x 2 cells); got " + std::to_string(H) + " x " +
+              std::to_string(W) + " padded to " + std::to_string(Hp) + " x " + std::to_string(Wp));
+}
+
+int sampt_raft_create(const char* const* names, const void* const* ptrs, int n, sampt_raft_t* out) {
+  if (!names || !ptrs || !out) return fail(SAMPT_ERR_ARG, "sampt_raft_create: bad arguments");
+  return create_handle<sampt_raft>("sampt_raft_create", out, [&](sampt_raft& h) { return h.e.init(make_map(names, ptrs, n)); });
+}
+void sampt_raft_destroy(sampt_raft_t h) { delete h; }
+
+int sampt_raft_workspace_bytes(sampt_raft_t h, int T, int H, int W, int max_pairs_in_flight, size_t* bytes) {
+  if (!h || !bytes || T < 1 || H < 1 || W < 1 || max_pairs_in_flight < 1) return fail(SAMPT_ERR_ARG, "sampt_raft_workspace_bytes: bad arguments");
+  SAMPT_TRY(raft_bad_size("sampt_raft_workspace_bytes", H, W));
+  Arena a(nullptr, 0);
+  int rc = h->e.flows(nullptr, T, H, W, 1, nullptr, nullptr, nullptr, max_pairs_in_flight, a, nullptr);
+  *bytes = a.peak + 256;
+  return rc;
+}
+
+int sampt_raft_flows_f32(sampt_raft_t h, const uint8_t* frames, int T, int H, int W, int iters, float* flows_fwd, float* flows_bwd,
+                         float* flow_low, void* ws, size_t ws_bytes, sampt_stream_t stream) {
+  if (!h || !frames || T < 1 || H < 1 || W < 1 || iters < 1 || !ws || (T > 1 && (!flows_fwd || !flows_bwd)))
+    return fail(SAMPT_ERR_ARG, "sampt_raft_flows_f32: bad arguments");
+  SAMPT_TRY(raft_bad_size("sampt_raft_flows_f32", H, W));
+  if (T == 1) return SAMPT_OK;
+  const int np = h->e.plan_pairs(T, H, W, T - 1, ws_bytes);
+  if (np < 1) return fail(SAMPT_ERR_WORKSPACE, "sampt_raft_flows_f32: the workspace does not hold one pair (sampt_raft_workspace_bytes)");
+  Arena a(ws, ws_bytes);
+  return h->e.flows(frames, T, H, W, iters, flows_fwd, flows_bwd, flow_low, np, a, (hipStream_t)stream);
+}
+
+int sampt_raft_chain(const float* flows_fwd, const float* flows_bwd, int T, int H, int W, const float* q, int n, float* traj,
+                     uint8_t* vis, sampt_stream_t stream) {
+  int rc = raft_chain(flows_fwd, flows_bwd, T, H, W, q, n, traj, vis, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_raft_chain: bad arguments") : rc;
+}
+
+static void raft_level_sizes(int h8, int w8, int lh[4], int lw[4]) {
+  lh[0] = h8, lw[0] = w8;
+  for (int l = 1; l < 4; ++l) lh[l] = lh[l - 1] / 2, lw[l] = lw[l - 1] / 2;
+}
+
+size_t sampt_raft_corr_pyramid_workspace_bytes(int h8, int w8) {
+  if (h8 < 1 || w8 < 1) return 0;
+  int lh[4], lw[4];
+  raft_level_sizes(h8, w8, lh, lw);
+  size_t b = 256;
+  for (int l = 1; l < 4; ++l) b += (size_t)lh[l] * lw[l] * 256 * 4 + 256;
+  return b;
+}
+
+int sampt_raft_corr_pyramid(const float* fmap1, const float* fmap2, int h8, int w8, float* const levels[4], void* ws, size_t ws_bytes,
+                            sampt_stream_t stream) {
+  if (!fmap1 || !fmap2 || !levels || !ws || h8 < 8 || w8 < 8 || !levels[0] || !levels[1] || !levels[2] || !levels[3])
+    return fail(SAMPT_ERR_ARG, "sampt_raft_corr_pyramid: bad arguments (the coarse grid must be at least 8 x 8)");
+  if (ws_bytes < sampt_raft_corr_pyramid_workspace_bytes(h8, w8)) return fail(SAMPT_ERR_WORKSPACE, "sampt_raft_corr_pyramid: workspace too small");
+  int lh[4], lw[4];
+  raft_level_sizes(h8, w8, lh, lw);
+  Arena a(ws, ws_bytes);
+  const float* pooled[4] = {fmap2, nullptr, nullptr, nullptr};
+  long s2[4] = {0, 0, 0, 0};
+  for (int l = 1; l < 4; ++l) {
+    float* p = a.f32((size_t)lh[l] * lw[l] * 256);
+    SAMPT_TRY(avgpool2x2_nhwc(pooled[l - 1], 1, lh[l - 1], lw[l - 1], 256, p, (hipStream_t)stream));
+    pooled[l] = p;
+  }
+  return raft_corr_levels(fmap1, 0, pooled, s2, 1, h8, w8, levels, (hipStream_t)stream);
+}
+
+int sampt_raft_lookup(const float* const levels[4], int h8, int w8, const float* coords, long m, float* out, sampt_stream_t stream) {
+  if (!levels || h8 < 8 || w8 < 8 || m < 1) return fail(SAMPT_ERR_ARG, "sampt_raft_lookup: bad arguments (the coarse grid must be at least 8 x 8)");
+  RaftLevels lv;
+  int lh[4], lw[4];
+  raft_level_sizes(h8, w8, lh, lw);
+  for (int l = 0; l < 4; ++l) lv.base[l] = levels[l], lv.h[l] = lh[l], lv.w[l] = lw[l];
+  int rc = raft_lookup(lv, coords, m, out, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_raft_lookup: bad arguments") : rc;
+}
+
+int sampt_raft_upsample(const float* flow_low, const float* mask, float mask_scale, int pairs, int h8, int w8, int H, int W, float* out,
+                        sampt_stream_t stream) {
+  int rc = raft_upsample(flow_low, mask, mask_scale, h8, w8, H, W, 0, pairs, out, nullptr, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_raft_upsample: bad arguments") : rc;
 }
 
 // ------------------------------------------------------------------------------------------- decoder

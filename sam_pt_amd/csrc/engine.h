@@ -135,6 +135,35 @@ struct CotEngine {
             hipStream_t s);
 };
 
+// RAFT (sam_pt/point_tracker/raft/): both encoders once per frame, then every pair-direction of the clip through the
+// 4-level all-pairs correlation and `iters` recurrent updates, a chunk of pairs at a time.  All convolutions run on the
+// exact-f32 implicit GEMM; weights as packed by pack.pack_raft (cnet's BatchNorms folded into its convolutions).
+struct RaftConv {
+  const float *w = nullptr, *b = nullptr;   // [Cout][KH*KW*Cin] (ci fastest), [Cout]
+  int cin = 0, cout = 0, kh = 1, kw = 1, stride = 1, ph = 0, pw = 0;
+};
+
+struct RaftEngine {
+  struct Enc {
+    RaftConv stem, blk[3][2][3], out;       // [layer][block][conv1, conv2, downsample]
+  } fnet, cnet;
+  RaftConv convc1, convc2, convf2, conv, zr[2], q[2], fh1, fh2, mask0, mask2;
+  const float *convf1_w = nullptr, *convf1_b = nullptr;   // [98][128], [128]
+  std::string error;
+
+  int init(const WeightMap& w);
+  // frames uint8 (T,3,H,W) -> flows_fwd / flows_bwd [T-1][2][H][W] (pair t: t -> t+1 and t+1 -> t), flow_low (optional)
+  // [2][T-1][2][H8][W8].  np = pairs per chunk (both directions of a pair travel together).
+  int flows(const uint8_t* frames, int T, int H, int W, int iters, float* fwd, float* bwd, float* flow_low, int np, Arena& ws,
+            hipStream_t s);
+  // the largest chunk (in pairs, <= max_pairs) whose workspace fits ws_bytes; 0 if not even one pair fits
+  int plan_pairs(int T, int H, int W, int max_pairs, size_t ws_bytes);
+};
+// corr levels of n pairs (RaftLevels layout over n "pair-directions"): level l [n][hw][h_l w_l] = fmap1 . pool_l(fmap2)^T / 16;
+// fmap1 [n][hw][256] with image stride s1 floats, pooled[l] [n][h_l w_l][256] with image stride s2[l]
+int raft_corr_levels(const float* fmap1, long s1, const float* const pooled[4], const long s2[4], int n, int h8, int w8,
+                     float* const out[4], hipStream_t s);
+
 // -------------------------------------------------------------------------------------------------
 struct VitConfig {
   int D = 768, depth = 12, heads = 12, grid = 64, window = 14, patch = 16, out_chans = 256, mlp_ratio = 4;

@@ -180,6 +180,33 @@ int pips_update(const float* delta, const float* gn_w, const float* gn_b, const 
 int pips_finalize(const float* ffeats, const float* vis_w, const float* vis_b, const float* coords, float stride,
                   int S, int n, float* traj, float* vis, hipStream_t s);
 
+// ---- raft.hip (RAFT point tracker, sam_pt/point_tracker/raft/; layouts in the file header) ---------------------------------
+struct RaftLevels {
+  const float* base[4];   // level l: [pair-directions][h8 * w8][h[l] * w[l]] f32
+  int h[4], w[4];
+};
+// uint8 (T,3,H,W) -> f32 NHWC4 (T,Hp,Wp,4) = 2 * (x / 255) - 1, replicate-padded by (Hp - H) / 2 before and the rest after
+int raft_prep_frames(const uint8_t* frames, int T, int H, int W, int Hp, int Wp, float* dst, hipStream_t s);
+int raft_add_relu(const float* a, const float* b, float* out, long n, hipStream_t s);
+int raft_split_ctx(const float* c, long rows, float* net, float* inp, hipStream_t s);
+// chunk of np pairs from pair p0: pair-direction j < np is (p0 + j -> p0 + j + 1), j >= np its reverse
+int raft_init_state(const float* net, const float* inp, int p0, int np, int h8, int w8, float* hx, float* coords1, float* flow,
+                    hipStream_t s);
+// out [M][352]: channel l * 81 + i * 9 + j = level l sampled at (x / 2^l + i - 4, y / 2^l + j - 4), [324, 352) zero; coords [M][2]
+int raft_lookup(const RaftLevels& lv, const float* coords, long M, float* out, hipStream_t s);
+// relu(Conv2d(2, 128, 7, padding=3)) over flow [nimg][h][wd][2]; w [98][128] with k = (ky * 7 + kx) * 2 + ci
+int raft_convf1(const float* flow, const float* w, const float* bias, float* out, int nimg, int h, int wd, hipStream_t s);
+int raft_gru_a(const float* zr, const float* hx, float* z, float* rhx, long M, hipStream_t s);
+int raft_gru_b(const float* q, const float* z, float* hx, float* hnet, long M, hipStream_t s);
+int raft_flow_update(const float* delta, float* coords1, float* flow, float* hx, int h8, int w8, long M, hipStream_t s);
+int raft_flow_low(const float* flow, float* out, int p0, int np, int npairs, int h8, int w8, hipStream_t s);
+// convex upsampling + un-padding to (2, H, W) per pair-direction; bwd == nullptr: np planes, all written to fwd[p0 ..]
+int raft_upsample(const float* flow, const float* mask, float mask_scale, int h8, int w8, int H, int W, int p0, int np, float* fwd,
+                  float* bwd, hipStream_t s);
+// flows [T-1][2][H][W], q [n][3] = (t, x, y) -> traj [T][n][2], vis bytes [T][n]   (tracker.py:46-88)
+int raft_chain(const float* fwd, const float* bwd, int T, int H, int W, const float* q, int n, float* traj, unsigned char* vis,
+               hipStream_t s);
+
 // ---- cotracker.hip (CoTracker v1 windows: SURVEY.md App. A-6; layouts in the file header) -------------------------------
 int cot_prepare(const float* qxy, const int* qt, const int* frame_map, float stride, int n, int T, float* xy0, int* fidx_pt,
                 float* traj_out, float* vis_out, hipStream_t s);

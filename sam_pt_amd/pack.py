@@ -221,6 +221,61 @@ def pack_pips2(sd: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
     return {k: v.to(device) for k, v in out.items()}
 
 
+def fold_batchnorm(w: torch.Tensor, b: torch.Tensor, sd: Dict[str, torch.Tensor], bn: str, eps: float = 1e-5):
+    """Conv2d followed by an eval-mode BatchNorm2d as one convolution: w' = w * g / sqrt(var + eps) per output channel,
+    b' = (b - mean) * g / sqrt(var + eps) + beta, formed in float64."""
+    g = sd[bn + ".weight"].double() / torch.sqrt(sd[bn + ".running_var"].double() + eps)
+    wf = w.double() * g.view(-1, 1, 1, 1)
+    bf = (b.double() - sd[bn + ".running_mean"].double()) * g + sd[bn + ".bias"].double()
+    return wf.float(), bf.float()
+
+
+def pack_raft(sd: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
+    """RAFT (csrc/engine_raft.hip): NHWC convolution weights, cnet's BatchNorms folded into the convolutions in front of
+    them, the channel paddings of the engine (stems 3 -> 4 input channels, convc1 324 -> 352, flow_head.conv2 2 -> 4 output
+    channels), the GRU's z and r convolutions of a pass stacked into one, convf1 transposed to [98][128]."""
+    out: Dict[str, torch.Tensor] = {}
+
+    def put(name, w, b, pad_cin_to=0):
+        out[name + ".weight"] = _khwc(w.float(), pad_cin_to)
+        out[name + ".bias"] = b.float().contiguous()
+
+    for enc in ("fnet", "cnet"):
+        batch = enc == "cnet"
+
+        def conv(name, bn=None, pad_cin_to=0):
+            w, b = sd[name + ".weight"], sd[name + ".bias"]
+            if batch and bn is not None:
+                w, b = fold_batchnorm(w, b, sd, bn)
+            put(name, w, b, pad_cin_to)
+
+        conv(enc + ".conv1", enc + ".norm1", pad_cin_to=4)
+        for li, stride in enumerate((1, 2, 2), start=1):
+            for bi in range(2):
+                p = f"{enc}.layer{li}.{bi}"
+                conv(p + ".conv1", p + ".norm1")
+                conv(p + ".conv2", p + ".norm2")
+                if bi == 0 and stride != 1:
+                    conv(p + ".downsample.0", p + ".norm3")
+        conv(enc + ".conv2")
+    u = "update_block."
+    put(u + "encoder.convc1", sd[u + "encoder.convc1.weight"], sd[u + "encoder.convc1.bias"], pad_cin_to=352)
+    for name in ("encoder.convc2", "encoder.convf2", "encoder.conv", "flow_head.conv1", "mask.0", "mask.2", "gru.convq1",
+                 "gru.convq2"):
+        put(u + name, sd[u + name + ".weight"], sd[u + name + ".bias"])
+    for n in ("1", "2"):
+        put(f"{u}gru.convzr{n}", torch.cat([sd[f"{u}gru.convz{n}.weight"], sd[f"{u}gru.convr{n}.weight"]]),
+            torch.cat([sd[f"{u}gru.convz{n}.bias"], sd[f"{u}gru.convr{n}.bias"]]))
+    out[u + "encoder.convf1.weight"] = _khwc(sd[u + "encoder.convf1.weight"].float()).t().contiguous()      # [98][128]
+    out[u + "encoder.convf1.bias"] = sd[u + "encoder.convf1.bias"].float().contiguous()
+    w2 = torch.zeros(4, 256, 3, 3)
+    w2[:2] = sd[u + "flow_head.conv2.weight"].float()
+    b2 = torch.zeros(4)
+    b2[:2] = sd[u + "flow_head.conv2.bias"].float()
+    put(u + "flow_head.conv2", w2, b2)
+    return {k: v.to(device) for k, v in out.items()}
+
+
 def window_row_map(grid: int, window: int, batches: int, rows: int = 0) -> torch.Tensor:
     """Row map of SAM's window_partition (App. A-3): entry ((b*nwin + w)*window^2 + i) = source token row
     b*grid^2 + y*grid + x, or -1 where the window hangs over the zero padding.  `rows` > 0 (a multiple of `window`):

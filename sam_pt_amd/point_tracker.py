@@ -647,3 +647,147 @@ class CoTrackerPointTracker(PointTracker):
         traj[:, :, 0] *= W / float(w)
         traj[:, :, 1] *= H / float(h)
         return traj.unsqueeze(0), visb.unsqueeze(0)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# RAFT
+# ------------------------------------------------------------------------------------------------------------------
+RAFT_MIN_SIDE = 128      # padded frame side below which the coarsest correlation level is a single cell
+
+
+def raft_padded_size(H: int, W: int) -> Tuple[int, int]:
+    """Frame size after InputPadder (raft_core/util.py:9-22): the next multiples of 8."""
+    return (H + 7) // 8 * 8, (W + 7) // 8 * 8
+
+
+def load_raft_checkpoint(checkpoint_path: Optional[str]):
+    """``Raftnet.__init__`` (raftnet.py:20-27): the checkpoint was saved from nn.DataParallel, so ``module.`` is removed
+    from every key.  None -> seeded random init."""
+    if checkpoint_path is None:
+        return None
+    if not os.path.exists(checkpoint_path):
+        raise FileNotFoundError(f"Raft checkpoint not found at {checkpoint_path}")          # raft/tracker.py:24-25
+    sd = torch.load(checkpoint_path, map_location="cpu")
+    return {k.replace("module.", ""): v for k, v in sd.items() if k != "module"}
+
+
+class RaftPointTracker(PointTracker):
+    """RAFT optical flow chained into point tracks, behind the constructor of
+    ``sam_pt.point_tracker.raft.RaftPointTracker`` (raft/tracker.py:17-27; configs/model/point_tracker/raft.yaml).
+    ``iters`` is an extra keyword; its default is the reference's hard-coded 32 (tracker.py:40-41).
+
+    Differences from the reference, on purpose:
+
+    * both encoders run ONCE per frame (the reference runs ``fnet`` four times and ``cnet`` twice on every inner frame);
+      the mask head and the convex upsampling run after the last iteration only;
+    * frames whose size padded to multiples of 8 is below 128 on either side are refused by name.  There the coarsest of
+      the four correlation levels is a single cell, ``bilinear_sampler`` divides by ``W - 1 = 0`` and the reference returns
+      NaN everywhere.
+    """
+
+    def __init__(self, checkpoint_path=None, iters: int = 32, state_dict: Optional[Dict[str, torch.Tensor]] = None,
+                 seed: int = 72, max_pairs_in_flight: int = 8):
+        super().__init__()
+        from .weights import init_raft_state_dict
+        self.checkpoint_path, self.iters = checkpoint_path, int(iters)
+        if self.iters < 1:
+            raise ValueError("RaftPointTracker: iters must be at least 1")
+        sd = state_dict if state_dict is not None else load_raft_checkpoint(checkpoint_path)
+        self._sd = sd if sd is not None else init_raft_state_dict(seed)
+        self.max_pairs_in_flight = max(1, int(max_pairs_in_flight))
+        self._h = None
+        self._device = None
+        self.stats = {"pair_directions": 0, "encoded_frames": 0}
+
+    def _ensure(self, device: torch.device):
+        if self._h is not None and self._device == device:
+            return
+        _lib.require_hip(device, "RaftPointTracker")
+        from .pack import pack_raft
+        lib = _lib.load()
+        self._w = pack_raft(self._sd, device)
+        names, ptrs, n = _lib.name_table(self._w)
+        h = C.c_void_p()
+        _lib.check(lib.sampt_raft_create(names, ptrs, n, C.byref(h)), "sampt_raft_create")
+        self._h, self._device, self._lib = h, device, lib
+
+    def __del__(self):
+        if getattr(self, "_h", None) is not None:
+            try:
+                self._lib.sampt_raft_destroy(self._h)
+            except Exception:
+                pass
+
+    @staticmethod
+    def check_frame_size(H: int, W: int):
+        Hp, Wp = raft_padded_size(H, W)
+        if Hp < RAFT_MIN_SIDE or Wp < RAFT_MIN_SIDE:
+            raise ValueError(f"RaftPointTracker: frames of {H} x {W} pixels (padded to {Hp} x {Wp}) are too small: RAFT needs at "
+                             f"least {RAFT_MIN_SIDE} pixels on both sides, or the coarsest of its 4 correlation levels is a "
+                             "single cell (the reference returns NaN there)")
+
+    @torch.no_grad()
+    @_lib.on_device(lambda self, frames, *a, **k: frames.device)
+    def flows(self, frames: torch.Tensor, iters: Optional[int] = None, return_low: bool = False,
+              workspace_pairs: Optional[int] = None):
+        """frames (T,3,H,W) uint8 on the device -> (flows_forward, flows_backward), each (T-1,2,H,W) f32: pair t holds the
+        flow from frame t to t+1 and from t+1 to t.  ``return_low`` adds the 1/8-resolution flows (2,T-1,2,Hp/8,Wp/8).
+        ``workspace_pairs`` sizes the workspace for that many pairs per chunk (default: ``max_pairs_in_flight``)."""
+        if frames.dim() == 5:
+            if frames.shape[0] != 1:
+                raise ValueError("RaftPointTracker.flows takes one clip (T,3,H,W)")
+            frames = frames[0]
+        assert frames.dtype == torch.uint8, "frames must be uint8 (PointTracker.forward contract)"
+        T, _, H, W = frames.shape
+        self.check_frame_size(H, W)
+        dev = frames.device
+        self._ensure(dev)
+        Hp, Wp = raft_padded_size(H, W)
+        fwd = torch.empty((max(T - 1, 0), 2, H, W), dtype=torch.float32, device=dev)
+        bwd = torch.empty_like(fwd)
+        low = torch.empty((2, max(T - 1, 0), 2, Hp // 8, Wp // 8), dtype=torch.float32, device=dev) if return_low else None
+        if T > 1:
+            pairs = min(T - 1, workspace_pairs if workspace_pairs is not None else self.max_pairs_in_flight)
+            nbytes = C.c_size_t()
+            _lib.check(self._lib.sampt_raft_workspace_bytes(self._h, T, H, W, pairs, C.byref(nbytes)), "sampt_raft_workspace_bytes")
+            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+            _lib.check(self._lib.sampt_raft_flows_f32(self._h, _lib.ptr(frames.contiguous()), T, H, W,
+                                                      self.iters if iters is None else int(iters), _lib.ptr(fwd), _lib.ptr(bwd),
+                                                      _lib.ptr(low), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                       "sampt_raft_flows_f32")
+            self.stats["pair_directions"] += 2 * (T - 1)
+            self.stats["encoded_frames"] += T
+        return (fwd, bwd, low) if return_low else (fwd, bwd)
+
+    @torch.no_grad()
+    @_lib.on_device(lambda self, fwd, *a, **k: fwd.device)
+    def chain(self, fwd: torch.Tensor, bwd: torch.Tensor, query_points: torch.Tensor):
+        """tracker.py:46-88 on the device: flows (T-1,2,H,W), query_points (N,3) = (t, x, y) -> trajectories (T,N,2) f32,
+        visibilities (T,N) bool."""
+        _lib.require_hip(fwd.device, "RaftPointTracker")
+        lib = _lib.load()
+        T, H, W = fwd.shape[0] + 1, fwd.shape[2], fwd.shape[3]
+        q = query_points.detach().to(device=fwd.device, dtype=torch.float32).contiguous()
+        N = q.shape[0]
+        traj = torch.empty((T, N, 2), dtype=torch.float32, device=fwd.device)
+        vis = torch.empty((T, N), dtype=torch.uint8, device=fwd.device)
+        if N > 0:
+            _lib.check(lib.sampt_raft_chain(_lib.ptr(fwd.contiguous()) if T > 1 else None, _lib.ptr(bwd.contiguous()) if T > 1 else None,
+                                            T, H, W, _lib.ptr(q), N, _lib.ptr(traj), _lib.ptr(vis), _lib.stream_ptr()),
+                       "sampt_raft_chain")
+        return traj, vis.bool()
+
+    @torch.no_grad()
+    @_lib.on_device(lambda self, rgbs, query_points: rgbs.device)
+    def forward(self, rgbs, query_points):
+        assert rgbs.dtype == torch.uint8, "rgbs must be uint8 (PointTracker.forward contract)"
+        B, T, _, H, W = rgbs.shape
+        self.check_frame_size(H, W)
+        _lib.require_hip(rgbs.device, "RaftPointTracker")
+        trajs, viss = [], []
+        for b in range(B):                                       # any batch size: one clip at a time
+            fwd, bwd = self.flows(rgbs[b])
+            t, v = self.chain(fwd, bwd, query_points[b])
+            trajs.append(t)
+            viss.append(v)
+        return torch.stack(trajs), torch.stack(viss)

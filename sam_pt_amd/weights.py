@@ -124,6 +124,67 @@ def init_pips_state_dict(seed: int = 72, S: int = PIPS_S, delta_scale: float = 0
 
 
 # --------------------------------------------------------------------------------------
+# RAFT (princeton-vl/RAFT @ aac9dd5, vendored by the reference under sam_pt/point_tracker/raft/raft_core)
+# --------------------------------------------------------------------------------------
+def init_raft_state_dict(seed: int = 72) -> "OrderedDict[str, torch.Tensor]":
+    """Random RAFT weights under the key names of ``raft-things.pth`` without the ``module.`` prefix (the module tree of
+    raft_core/raft.py:57-59: ``fnet`` with InstanceNorm — no parameters —, ``cnet`` with BatchNorm, ``update_block``).
+
+    The encoders keep their own kaiming fan-out init (extractor.py:149-151) and the update block PyTorch's default, which
+    already gives flows of several pixels that converge over the 32 iterations (figures: DESIGN.md §4).  ``cnet``'s
+    BatchNorms get non-trivial running statistics and affine terms, so that folding them into the convolutions
+    (pack.pack_raft) is exercised.  ``norm3`` and ``downsample.1`` of a strided block are one module registered twice, as
+    in the checkpoint."""
+    w = _Init(seed)
+
+    def bn(prefix, dim):
+        w.normal(prefix + ".weight", (dim,), 0.1, mean=1.0)
+        w.normal(prefix + ".bias", (dim,), 0.1)
+        w.normal(prefix + ".running_mean", (dim,), 0.2)
+        w.uniform(prefix + ".running_var", (dim,), 0.5)
+        w.sd[prefix + ".running_var"] = w.sd[prefix + ".running_var"] + 1.0          # in [0.5, 1.5]
+        w.sd[prefix + ".num_batches_tracked"] = torch.tensor(1000, dtype=torch.long)
+
+    for enc, out_dim, batch in (("fnet", 256, False), ("cnet", 256, True)):
+        if batch:
+            bn(enc + ".norm1", 64)
+        w.conv(enc + ".conv1", 64, 3, 7, 7, kaiming_fan_out=True)
+        in_planes = 64
+        for li, (dim, stride) in enumerate([(64, 1), (96, 2), (128, 2)], start=1):
+            for bi in range(2):
+                cin = in_planes if bi == 0 else dim
+                p = f"{enc}.layer{li}.{bi}"
+                w.conv(p + ".conv1", dim, cin, 3, 3, kaiming_fan_out=True)
+                w.conv(p + ".conv2", dim, dim, 3, 3, kaiming_fan_out=True)
+                if batch:
+                    bn(p + ".norm1", dim)
+                    bn(p + ".norm2", dim)
+                if bi == 0 and stride != 1:
+                    if batch:
+                        bn(p + ".norm3", dim)
+                    w.conv(p + ".downsample.0", dim, cin, 1, 1, kaiming_fan_out=True)
+                    if batch:
+                        for k in ("weight", "bias", "running_mean", "running_var", "num_batches_tracked"):
+                            w.sd[f"{p}.downsample.1.{k}"] = w.sd[f"{p}.norm3.{k}"]
+            in_planes = dim
+        w.conv(enc + ".conv2", out_dim, 128, 1, 1, kaiming_fan_out=True)
+    u = "update_block."
+    w.conv(u + "encoder.convc1", 256, 324, 1, 1)
+    w.conv(u + "encoder.convc2", 192, 256, 3, 3)
+    w.conv(u + "encoder.convf1", 128, 2, 7, 7)
+    w.conv(u + "encoder.convf2", 64, 128, 3, 3)
+    w.conv(u + "encoder.conv", 126, 256, 3, 3)
+    for n, (kh, kw) in (("1", (1, 5)), ("2", (5, 1))):
+        for g in ("z", "r", "q"):
+            w.conv(f"{u}gru.conv{g}{n}", 128, 384, kh, kw)
+    w.conv(u + "flow_head.conv1", 256, 128, 3, 3)
+    w.conv(u + "flow_head.conv2", 2, 256, 3, 3)
+    w.conv(u + "mask.0", 256, 128, 3, 3)
+    w.conv(u + "mask.2", 576, 256, 1, 1)
+    return w.sd
+
+
+# --------------------------------------------------------------------------------------
 # CoTracker v1 (facebookresearch/co-tracker @ 4f297a9, requirements.txt:29 — third-party, absent from the reference tree)
 # --------------------------------------------------------------------------------------
 COTRACKER_HIDDEN = 384
