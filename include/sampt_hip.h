@@ -27,12 +27,14 @@ extern "C" {
 #define SAMPT_ERR_HIP (-2)
 #define SAMPT_ERR_UNSUPPORTED (-3)
 #define SAMPT_ERR_WORKSPACE (-4)
+#define SAMPT_ERR_CAPACITY (-5)   /* more results than the capacity the caller gave (nothing is truncated silently) */
 
 typedef void* sampt_stream_t; /* hipStream_t */
 typedef struct sampt_pips* sampt_pips_t;
 typedef struct sampt_pips2* sampt_pips2_t;
 typedef struct sampt_cotracker* sampt_cotracker_t;
 typedef struct sampt_raft* sampt_raft_t;
+typedef struct sampt_sg* sampt_sg_t;
 typedef struct sampt_vit* sampt_vit_t;
 typedef struct sampt_dec* sampt_dec_t;
 
@@ -187,6 +189,54 @@ int sampt_raft_lookup(const float* const levels_dev[4], int h8, int w8, const fl
                       sampt_stream_t stream);
 int sampt_raft_upsample(const float* flow_low_dev, const float* mask_dev, float mask_scale, int pairs, int h8, int w8, int H,
                         int W, float* out_dev, sampt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * seam 1e — SuperGlue point tracker (sam_pt/point_tracker/superglue/{tracker.py, models/superpoint.py, models/superglue.py}).
+ * Weights after sam_pt_amd.pack.pack_superglue: "superpoint.<conv>.{weight,bias}" as [Cout][KH][KW][Cin] (conv1a's Cin
+ * zero-padded 1 -> 4, convPb's Cout 65 -> 68), "superglue.kenc.<0..4>", "superglue.gnn.<l>.{qkv,merge,mlp0,mlp1}",
+ * "superglue.final_proj" as [N][K] with every eval-mode BatchNorm1d folded in and the attention heads permuted from the
+ * reference's interleaved channels (d * 4 + h) to blocked ones (h * 64 + d); "superglue.bin_score" [1].
+ *   detect : frames_dev uint8 (T,3,H,W) -> per frame the keypoints (x, y) [T][cap][2] in torch.nonzero's order, their scores
+ *            [T][cap], sampled descriptors [T][cap][256] (rows, not channels-first) and counts [T] on the device AND on the host
+ *            (one stream synchronisation).  dense_dev (optional) receives the score maps [T][8 (H/8)][8 (W/8)].  A frame with
+ *            more than cap keypoints makes the call return SAMPT_ERR_CAPACITY (counts_host then holds the true counts; no
+ *            descriptor has been sampled).
+ *   match  : SuperGlue on one pair -> matches0_dev int32 [n0] (-1 = none), mscores0_dev [n0].  n0 == 0 or n1 == 0: all -1 / 0.
+ *            Optional copies for tests: gnn_out_dev [n0 + n1][256] (descriptors after the last GNN layer, blocked-head
+ *            independent), scores_out_dev [n0][n1] (the matrix Sinkhorn starts from), uv_out_dev [n0 + 1 + n1 + 1].
+ * Test / building-block entry points: nms (dense score maps -> keypoints, as inside detect), sample_descriptors (raw dense
+ * descriptor map [h8 * w8][256] NHWC + n keypoints -> [n][256]), attention (q [N][heads * 64], k / v [M][heads * 64], blocked
+ * heads, scale 1 / 8), sinkhorn (S [N][M] -> u [N + 1], v [M + 1]), mutual_match (S, u, v -> matches0, mscores0; ws of
+ * (2 N + M) * 4 bytes), select (per-mask ordered lists of matched keypoint-1 indices inside / outside the mask) and gather.
+ * --------------------------------------------------------------------------------------------------------- */
+int sampt_sg_create(const char* const* names, const void* const* ptrs, int n, sampt_sg_t* out);
+void sampt_sg_destroy(sampt_sg_t h);
+int sampt_sg_workspace_bytes(sampt_sg_t h, int T, int H, int W, int n0, int n1, size_t* detect_bytes, size_t* match_bytes);
+int sampt_sg_detect(sampt_sg_t h, const uint8_t* frames_dev, int T, int H, int W, int nms_radius, float keypoint_threshold,
+                    int remove_borders, int cap, float* kpts_dev, float* kscores_dev, float* desc_dev, int32_t* counts_dev,
+                    int32_t* counts_host, float* dense_dev, void* workspace_dev, size_t workspace_bytes, sampt_stream_t stream);
+int sampt_sg_match(sampt_sg_t h, const float* kpts0_dev, const float* kscores0_dev, const float* desc0_dev, int n0,
+                   const float* kpts1_dev, const float* kscores1_dev, const float* desc1_dev, int n1, int H, int W,
+                   int sinkhorn_iterations, float match_threshold, int32_t* matches0_dev, float* mscores0_dev, float* gnn_out_dev,
+                   float* scores_out_dev, float* uv_out_dev, void* workspace_dev, size_t workspace_bytes, sampt_stream_t stream);
+size_t sampt_sg_nms_workspace_bytes(int nimg, int Hs, int Ws);
+int sampt_sg_nms(const float* scores_dev, int nimg, int Hs, int Ws, int nms_radius, float keypoint_threshold, int remove_borders,
+                 int cap, float* kpts_dev, float* kscores_dev, int32_t* counts_dev, int32_t* counts_host, void* workspace_dev,
+                 size_t workspace_bytes, sampt_stream_t stream);
+int sampt_sg_sample_descriptors(const float* dmap_dev, int h8, int w8, const float* kpts_dev, int n, float* out_dev,
+                                sampt_stream_t stream);
+int sampt_sg_attention(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, int N, int M, int heads,
+                       sampt_stream_t stream);
+int sampt_sg_sinkhorn(const float* scores_dev, int N, int M, const float* bin_score_dev, int iters, float* u_dev, float* v_dev,
+                      sampt_stream_t stream);
+int sampt_sg_mutual_match(const float* scores_dev, int N, int M, const float* u_dev, const float* v_dev, float match_threshold,
+                          int32_t* matches0_dev, float* mscores0_dev, void* workspace_dev, size_t workspace_bytes,
+                          sampt_stream_t stream);
+int sampt_sg_select(const int32_t* matches0_dev, int n0, const float* kpts1_dev, const float* masks_dev, int n_masks, int H, int W,
+                    int cap, int32_t* lists_dev, int32_t* counts_dev, sampt_stream_t stream);
+int sampt_sg_gather(const float* query_xy_dev, const float* kpts_dev, int kp_cap, const int32_t* lists_dev, int list_cap,
+                    const int32_t* counts_dev, const int32_t* draw_dev, int T, int n_masks, int n_pos, int n_neg, float* traj_dev,
+                    float* vis_dev, sampt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * seam 2a — SAM image encoder = SamPredictor.set_image (Sam.preprocess + ImageEncoderViT, Appendix A-1..A-3).

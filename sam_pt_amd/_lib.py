@@ -22,6 +22,9 @@ class SamptError(RuntimeError):
     pass
 
 
+ERR_CAPACITY = -5     # SAMPT_ERR_CAPACITY: more results than the capacity the caller gave
+
+
 class VitConfigC(C.Structure):
     _fields_ = [("embed_dim", c_int), ("depth", c_int), ("num_heads", c_int), ("grid", c_int), ("window", c_int),
                 ("patch", c_int), ("out_chans", c_int), ("mlp_ratio", c_int), ("img_size", c_int),
@@ -54,6 +57,21 @@ _SIGS = {
     "sampt_raft_corr_pyramid": (c_int, [_P, _P, c_int, c_int, C.POINTER(_P), _P, c_size_t, _P]),
     "sampt_raft_lookup": (c_int, [C.POINTER(_P), c_int, c_int, _P, C.c_long, _P, _P]),
     "sampt_raft_upsample": (c_int, [_P, _P, c_float, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "sampt_sg_create": (c_int, [C.POINTER(c_char_p), C.POINTER(_P), c_int, C.POINTER(_P)]),
+    "sampt_sg_destroy": (None, [_P]),
+    "sampt_sg_workspace_bytes": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, C.POINTER(c_size_t), C.POINTER(c_size_t)]),
+    "sampt_sg_detect": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_int, c_int, _P, _P, _P, _P, C.POINTER(c_int), _P, _P,
+                                c_size_t, _P]),
+    "sampt_sg_match": (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, _P, _P, _P,
+                               c_size_t, _P]),
+    "sampt_sg_nms_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "sampt_sg_nms": (c_int, [_P, c_int, c_int, c_int, c_int, c_float, c_int, c_int, _P, _P, _P, C.POINTER(c_int), _P, c_size_t, _P]),
+    "sampt_sg_sample_descriptors": (c_int, [_P, c_int, c_int, _P, c_int, _P, _P]),
+    "sampt_sg_attention": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "sampt_sg_sinkhorn": (c_int, [_P, c_int, c_int, _P, c_int, _P, _P, _P]),
+    "sampt_sg_mutual_match": (c_int, [_P, c_int, c_int, _P, _P, c_float, _P, _P, _P, c_size_t, _P]),
+    "sampt_sg_select": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "sampt_sg_gather": (c_int, [_P, _P, c_int, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "sampt_cotracker_create": (c_int, [C.POINTER(c_char_p), C.POINTER(_P), c_int, c_int, c_int, C.POINTER(_P)]),
     "sampt_cotracker_destroy": (None, [_P]),
     "sampt_resize_frames_f32": (c_int, [_P, c_int, C.c_long, c_int, c_int, _P, c_int, c_int, _P]),

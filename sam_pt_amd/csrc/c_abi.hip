@@ -56,6 +56,7 @@ struct sampt_pips {
 struct sampt_pips2 { Pips2Engine e; };
 struct sampt_cotracker { CotEngine e; };
 struct sampt_raft { RaftEngine e; };
+struct sampt_sg { SgEngine e; };
 struct sampt_vit { VitEngine e; };
 // hipGraph cache of the per-(frame, object) decode chain (north_star: "hipGraph capture of the per-frame decode"): one
 // instantiated graph per distinct call signature (every scalar AND every pointer of sampt_sam_track_decode_graph).
@@ -511,6 +512,128 @@ int sampt_raft_chain(const float* flows_fwd, const float* flows_bwd, int T, int 
                      uint8_t* vis, sampt_stream_t stream) {
   int rc = raft_chain(flows_fwd, flows_bwd, T, H, W, q, n, traj, vis, (hipStream_t)stream);
   return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_raft_chain: bad arguments") : rc;
+}
+
+// ------------------------------------------------------------------------------------------- SuperGlue tracker
+int sampt_sg_create(const char* const* names, const void* const* ptrs, int n, sampt_sg_t* out) {
+  if (!names || !ptrs || !out) return fail(SAMPT_ERR_ARG, "sampt_sg_create: bad arguments");
+  return create_handle<sampt_sg>("sampt_sg_create", out, [&](sampt_sg& h) { return h.e.init(make_map(names, ptrs, n)); });
+}
+void sampt_sg_destroy(sampt_sg_t h) { delete h; }
+
+int sampt_sg_workspace_bytes(sampt_sg_t h, int T, int H, int W, int n0, int n1, size_t* detect_bytes, size_t* match_bytes) {
+  if (!h || T < 1 || H < 8 || W < 8 || n0 < 0 || n1 < 0) return fail(SAMPT_ERR_ARG, "sampt_sg_workspace_bytes: bad arguments");
+  if (detect_bytes) {
+    Arena a(nullptr, 0);
+    SgDetectCfg c;
+    c.cap = 1;
+    SAMPT_TRY(h->e.detect(nullptr, T, H, W, c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, a, nullptr));
+    *detect_bytes = a.peak + 256;
+  }
+  if (match_bytes) {
+    Arena a(nullptr, 0);
+    SAMPT_TRY(h->e.match(nullptr, nullptr, nullptr, n0, nullptr, nullptr, nullptr, n1, H, W, 1, 0.f, nullptr, nullptr, nullptr, nullptr,
+                         nullptr, a, nullptr));
+    *match_bytes = a.peak + 256;
+  }
+  return SAMPT_OK;
+}
+
+static int sg_capacity(const char* who, const int* counts_host, int n, int cap) {
+  for (int i = 0; i < n; ++i)
+    if (counts_host[i] > cap)
+      return fail(SAMPT_ERR_CAPACITY, std::string(who) + ": image " + std::to_string(i) + " has " + std::to_string(counts_host[i]) +
+                                          " keypoints, the capacity is " + std::to_string(cap));
+  return SAMPT_OK;
+}
+
+int sampt_sg_detect(sampt_sg_t h, const uint8_t* frames, int T, int H, int W, int nms_radius, float keypoint_threshold,
+                    int remove_borders, int cap, float* kpts, float* kscores, float* desc, int32_t* counts_dev, int32_t* counts_host,
+                    float* dense, void* ws, size_t ws_bytes, sampt_stream_t stream) {
+  if (!h || !frames || !kpts || !kscores || !desc || !counts_dev || !counts_host || !ws || T < 1 || H < 8 || W < 8 || cap < 1 ||
+      nms_radius < 0)
+    return fail(SAMPT_ERR_ARG, "sampt_sg_detect: bad arguments");
+  SgDetectCfg c;
+  c.nms_radius = nms_radius, c.threshold = keypoint_threshold, c.border = remove_borders, c.cap = cap;
+  Arena a(ws, ws_bytes);
+  int rc = h->e.detect(frames, T, H, W, c, kpts, kscores, desc, counts_dev, counts_host, dense, a, (hipStream_t)stream);
+  if (rc == SAMPT_ERR_CAPACITY) return sg_capacity("sampt_sg_detect", counts_host, T, cap);
+  if (rc == SAMPT_ERR_WORKSPACE) return fail(rc, "sampt_sg_detect: workspace too small (sampt_sg_workspace_bytes)");
+  if (rc == SAMPT_ERR_UNSUPPORTED) return fail(rc, "sampt_sg_detect: nms_radius above 16 or more than 4096 score rows");
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_sg_detect: bad arguments") : rc;
+}
+
+int sampt_sg_match(sampt_sg_t h, const float* kp0, const float* sc0, const float* d0, int n0, const float* kp1, const float* sc1,
+                   const float* d1, int n1, int H, int W, int iters, float thr, int32_t* matches0, float* mscores0, float* gnn_out,
+                   float* scores_out, float* uv_out, void* ws, size_t ws_bytes, sampt_stream_t stream) {
+  if (!h || n0 < 0 || n1 < 0 || iters < 0 || H < 1 || W < 1 || (n0 > 0 && (!matches0 || !mscores0)))
+    return fail(SAMPT_ERR_ARG, "sampt_sg_match: bad arguments");
+  if (n0 > 0 && n1 > 0 && (!kp0 || !sc0 || !d0 || !kp1 || !sc1 || !d1 || !ws)) return fail(SAMPT_ERR_ARG, "sampt_sg_match: null pointer");
+  if (n0 == 0 || n1 == 0) return sg_no_match(n0, matches0, mscores0, (hipStream_t)stream);   // no workspace, no kernel
+  Arena a(ws, ws_bytes);
+  int rc = h->e.match(kp0, sc0, d0, n0, kp1, sc1, d1, n1, H, W, iters, thr, matches0, mscores0, gnn_out, scores_out, uv_out, a,
+                      (hipStream_t)stream);
+  if (rc == SAMPT_ERR_WORKSPACE) return fail(rc, "sampt_sg_match: workspace too small (sampt_sg_workspace_bytes)");
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_sg_match: bad arguments") : rc;
+}
+
+size_t sampt_sg_nms_workspace_bytes(int nimg, int Hs, int Ws) {
+  return (nimg < 1 || Hs < 1 || Ws < 1) ? 0 : sg_nms_workspace_bytes(nimg, Hs, Ws);
+}
+
+int sampt_sg_nms(const float* scores, int nimg, int Hs, int Ws, int nms_radius, float keypoint_threshold, int remove_borders, int cap,
+                 float* kpts, float* kscores, int32_t* counts_dev, int32_t* counts_host, void* ws, size_t ws_bytes, sampt_stream_t stream) {
+  if (!counts_host) return fail(SAMPT_ERR_ARG, "sampt_sg_nms: bad arguments");
+  int rc = sg_nms_compact(scores, nimg, Hs, Ws, nms_radius, keypoint_threshold, remove_borders, cap, kpts, kscores, counts_dev, ws,
+                          ws_bytes, (hipStream_t)stream);
+  if (rc == SAMPT_ERR_ARG) return fail(rc, "sampt_sg_nms: bad arguments");
+  if (rc == SAMPT_ERR_UNSUPPORTED) return fail(rc, "sampt_sg_nms: nms_radius above 16 or more than 4096 rows");
+  if (rc == SAMPT_ERR_WORKSPACE) return fail(rc, "sampt_sg_nms: workspace too small (sampt_sg_nms_workspace_bytes)");
+  if (rc != SAMPT_OK) return rc;
+  if (hipMemcpyAsync(counts_host, counts_dev, (size_t)nimg * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
+      hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
+    return fail(SAMPT_ERR_HIP, "sampt_sg_nms: copying the counts failed");
+  return sg_capacity("sampt_sg_nms", counts_host, nimg, cap);
+}
+
+int sampt_sg_sample_descriptors(const float* dmap, int h8, int w8, const float* kpts, int n, float* out, sampt_stream_t stream) {
+  if (n == 0) return SAMPT_OK;
+  int rc = n < 0 ? SAMPT_ERR_ARG : sg_sample_descriptors(dmap, 1, h8, w8, kpts, nullptr, n, n, out, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_sg_sample_descriptors: bad arguments") : rc;
+}
+
+int sampt_sg_attention(const float* q, const float* k, const float* v, float* out, int N, int M, int heads, sampt_stream_t stream) {
+  int rc = sg_attention(q, heads * 64, k, v, heads * 64, out, heads * 64, N, M, heads, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_sg_attention: bad arguments (N, M, heads >= 1)") : rc;
+}
+
+int sampt_sg_sinkhorn(const float* scores, int N, int M, const float* bin, int iters, float* u, float* v, sampt_stream_t stream) {
+  int rc = sg_sinkhorn(scores, M, N, M, bin, iters, u, v, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_sg_sinkhorn: bad arguments (N, M >= 1)") : rc;
+}
+
+int sampt_sg_mutual_match(const float* scores, int N, int M, const float* u, const float* v, float thr, int32_t* matches0,
+                          float* mscores0, void* ws, size_t ws_bytes, sampt_stream_t stream) {
+  if (N < 0 || M < 0) return fail(SAMPT_ERR_ARG, "sampt_sg_mutual_match: bad arguments");
+  if (N == 0 || M == 0) return sg_no_match(N, matches0, mscores0, (hipStream_t)stream);
+  if (!ws || ws_bytes < ((size_t)2 * N + M) * 4) return fail(SAMPT_ERR_WORKSPACE, "sampt_sg_mutual_match: workspace of (2 N + M) * 4 bytes");
+  float* max0 = (float*)ws;
+  int* idx0 = (int*)ws + N;
+  int* idx1 = idx0 + N;
+  int rc = sg_match_from_scores(scores, M, N, M, u, v, thr, max0, idx0, idx1, matches0, mscores0, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_sg_mutual_match: bad arguments") : rc;
+}
+
+int sampt_sg_select(const int32_t* matches0, int n0, const float* kpts1, const float* masks, int n_masks, int H, int W, int cap,
+                    int32_t* lists, int32_t* counts, sampt_stream_t stream) {
+  int rc = sg_select_lists(matches0, n0, kpts1, masks, n_masks, H, W, cap, lists, counts, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_sg_select: bad arguments") : rc;
+}
+
+int sampt_sg_gather(const float* query_xy, const float* kpts, int kp_cap, const int32_t* lists, int list_cap, const int32_t* counts,
+                    const int32_t* draw, int T, int n_masks, int n_pos, int n_neg, float* traj, float* vis, sampt_stream_t stream) {
+  int rc = sg_gather(query_xy, kpts, kp_cap, lists, list_cap, counts, draw, T, n_masks, n_pos, n_neg, traj, vis, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_sg_gather: bad arguments") : rc;
 }
 
 static void raft_level_sizes(int h8, int w8, int lh[4], int lw[4]) {

@@ -11,6 +11,9 @@
 #define SAMPT_ERR_HIP (-2)       // a HIP runtime call failed (see sampt_last_error)
 #define SAMPT_ERR_UNSUPPORTED (-3)
 #define SAMPT_ERR_WORKSPACE (-4) // caller-provided workspace too small
+#ifndef SAMPT_ERR_CAPACITY
+#define SAMPT_ERR_CAPACITY (-5)  // more results than the capacity the caller gave
+#endif
 
 typedef _Float16 half_t;
 typedef float f32x4 __attribute__((ext_vector_type(4)));

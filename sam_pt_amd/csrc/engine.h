@@ -165,6 +165,37 @@ int raft_corr_levels(const float* fmap1, long s1, const float* const pooled[4], 
                      float* const out[4], hipStream_t s);
 
 // -------------------------------------------------------------------------------------------------
+// SuperPoint + SuperGlue (engine_superglue.hip).  Weights after sam_pt_amd.pack.pack_superglue.
+struct SgLinear {
+  const float *w = nullptr, *b = nullptr;   // [N][K], [N]
+  int n = 0, k = 0;
+};
+struct SgDetectCfg {
+  int nms_radius = 4, border = 4, cap = 0;
+  float threshold = 0.005f;
+};
+struct SgEngine {
+  RaftConv sp[8], convPa, convPb, convDa, convDb;    // convPb: 65 outputs zero-padded to 68
+  SgLinear kenc[5];
+  struct Layer { SgLinear qkv, merge, mlp0, mlp1; } gnn[18];
+  int cross[18];
+  SgLinear final_proj;
+  const float* bin_score = nullptr;
+  std::string error;
+
+  int init(const WeightMap& w);
+  // frames uint8 (T,3,H,W) -> kpts [T][cap][2], kscores [T][cap], desc [T][cap][256], counts_dev [T] and counts_host [T] (one
+  // stream synchronisation); dense (optional) [T][8 (H/8)][8 (W/8)] score maps.  SAMPT_ERR_WORKSPACE... see c_abi for the codes
+  int detect(const uint8_t* frames, int T, int H, int W, const SgDetectCfg& c, float* kpts, float* kscores, float* desc,
+             int* counts_dev, int* counts_host, float* dense, Arena& ws, hipStream_t s);
+  // one pair: keypoints / scores / descriptors of both images -> matches0 [n0], mscores0 [n0]; optional copies for tests:
+  // gnn_out [n0 + n1][256] (the descriptors after the last layer), scores_out [n0][n1] (before Sinkhorn), uv_out [n0 + 1 + n1 + 1]
+  int match(const float* kp0, const float* sc0, const float* d0, int n0, const float* kp1, const float* sc1, const float* d1, int n1,
+            int H, int W, int iters, float thr, int* matches0, float* mscores0, float* gnn_out, float* scores_out, float* uv_out,
+            Arena& ws, hipStream_t s);
+};
+
+// -------------------------------------------------------------------------------------------------
 struct VitConfig {
   int D = 768, depth = 12, heads = 12, grid = 64, window = 14, patch = 16, out_chans = 256, mlp_ratio = 4;
   int img = 1024;

@@ -207,6 +207,39 @@ int raft_upsample(const float* flow, const float* mask, float mask_scale, int h8
 int raft_chain(const float* fwd, const float* bwd, int T, int H, int W, const float* q, int n, float* traj, unsigned char* vis,
                hipStream_t s);
 
+// ---- superglue.hip (SuperGlue point tracker, sam_pt/point_tracker/superglue/; layouts in the file header) --------------------
+// uint8 (T,3,H,W) -> f32 NHWC4 (T,H,W,4): channel 0 = uint8(0.2989 r + 0.587 g + 0.114 b) / 255, the rest zero
+int sg_grey(const uint8_t* frames, int T, int H, int W, float* dst, hipStream_t s);
+int maxpool2x2_nhwc(const float* src, int n, int h, int w, int C, float* dst, hipStream_t s);
+// logits [nimg * h8 * w8][ld >= 65] -> dense score maps [nimg][8 h8][8 w8] (softmax over 65, dustbin dropped, depth-to-space)
+int sg_scores(const float* logits, int ld, int nimg, int h8, int w8, float* dense, hipStream_t s);
+// simple_nms + threshold (>) + remove_borders + row-major compaction: kpts [nimg][cap][2] (x, y), kscores [nimg][cap], count
+// [nimg] = the true number of survivors (entries at or beyond cap are not written).  radius <= 16, Hs <= 4096
+size_t sg_nms_workspace_bytes(int nimg, int Hs, int Ws);
+int sg_nms_compact(const float* scores, int nimg, int Hs, int Ws, int radius, float thr, int border, int cap, float* kpts,
+                   float* kscores, int* count, void* ws, size_t ws_bytes, hipStream_t s);
+// dmap [nimg][h8 * w8][256] (raw) -> out [nimg][cap][256] for the first min(count[f], cap) keypoints of every image (count ==
+// nullptr: cap of them); launch_n = the largest count (grid size)
+int sg_sample_descriptors(const float* dmap, int nimg, int h8, int w8, const float* kpts, const int* count, int cap, int launch_n,
+                          float* out, hipStream_t s);
+int sg_kenc_input(const float* kpts, const float* scores, int n, int H, int W, float* out, hipStream_t s);
+// out[i][h * 64 + d] = softmax_j(<q_i, k_j> / 8) v_j per head h, any N >= 1 queries and M >= 1 keys (row strides in floats)
+int sg_attention(const float* q, int ldq, const float* k, const float* v, int ldkv, float* out, int ldo, int N, int M, int heads,
+                 hipStream_t s);
+// log_optimal_transport's u [N + 1] and v [M + 1] after `iters` iterations; bin: device scalar
+int sg_sinkhorn(const float* S, int ld, int N, int M, const float* bin, int iters, float* u, float* v, hipStream_t s);
+// matches0 / matching_scores0 [N] from S, u, v; scratch max0 [N], idx0 [N], idx1 [M]
+int sg_match_from_scores(const float* S, int ld, int N, int M, const float* u, const float* v, float thr, float* max0, int* idx0,
+                         int* idx1, int* matches0, float* mscores0, hipStream_t s);
+int sg_no_match(int n, int* matches0, float* mscores0, hipStream_t s);
+// per-mask ordered lists of the matched keypoint-1 indices inside (0) / outside (1) the mask: lists [n_masks][2][cap], counts [n_masks][2]
+int sg_select_lists(const int* matches0, int n0, const float* kpts1, const float* masks, int n_masks, int H, int W, int cap,
+                    int* lists, int* counts, hipStream_t s);
+// lists [T-1][n_masks][2][list_cap], counts [T-1][n_masks][2], draw [T-1][n_masks][n_pos + n_neg] (list entry, < 0 = padding),
+// kpts [T][kp_cap][2], query_xy [n_masks * P][2] -> traj [T][n_masks * P][2], vis [T][n_masks * P]
+int sg_gather(const float* query_xy, const float* kpts, int kp_cap, const int* lists, int list_cap, const int* counts, const int* draw,
+              int T, int n_masks, int n_pos, int n_neg, float* traj, float* vis, hipStream_t s);
+
 // ---- cotracker.hip (CoTracker v1 windows: SURVEY.md App. A-6; layouts in the file header) -------------------------------
 int cot_prepare(const float* qxy, const int* qt, const int* frame_map, float stride, int n, int T, float* xy0, int* fidx_pt,
                 float* traj_out, float* vis_out, hipStream_t s);

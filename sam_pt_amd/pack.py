@@ -276,6 +276,66 @@ def pack_raft(sd: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
     return {k: v.to(device) for k, v in out.items()}
 
 
+def fold_batchnorm1d(w: torch.Tensor, b: torch.Tensor, sd: Dict[str, torch.Tensor], bn: str, eps: float = 1e-5):
+    """Conv1d(kernel 1) [out][in] followed by an eval-mode BatchNorm1d as one affine map, formed in float64 (returned as
+    float64: the caller rounds once, after any further reordering)."""
+    g = sd[bn + ".weight"].double() / torch.sqrt(sd[bn + ".running_var"].double() + eps)
+    return w.double() * g[:, None], (b.double() - sd[bn + ".running_mean"].double()) * g + sd[bn + ".bias"].double()
+
+
+def superglue_head_permutation(dim: int = 256, heads: int = 4) -> torch.Tensor:
+    """perm[h * (dim / heads) + d] = d * heads + h: MultiHeadedAttention's ``view(b, dim / heads, heads, n)`` interleaves
+    the heads over the channels (superglue.py:108); the attention kernel wants each head's channels contiguous."""
+    hd = dim // heads
+    return (torch.arange(hd)[None, :] * heads + torch.arange(heads)[:, None]).reshape(-1)
+
+
+def pack_superglue(sp_sd: Dict[str, torch.Tensor], sg_sd: Dict[str, torch.Tensor], device, dtype=torch.float32) -> Dict[str, torch.Tensor]:
+    """SuperPoint + SuperGlue (csrc/engine_superglue.hip).  SuperPoint: NHWC convolution weights, conv1a's single input
+    channel zero-padded to 4, convPb's 65 outputs to 68.  SuperGlue: Conv1d(kernel 1) weights as [out][in]; every eval-mode
+    BatchNorm1d folded into the convolution in front of it in float64; the keypoint encoder's first layer K-padded 3 -> 4;
+    per GNN layer the three projections stacked into one [768][256] with their rows permuted from interleaved to blocked
+    heads, and the merge convolution's columns permuted the same way.  Everything runs on the exact-f32 GEMM, so no
+    split-fp16 operand images are made.  ``dtype=torch.float64`` keeps the folded weights unrounded (tests)."""
+    out: Dict[str, torch.Tensor] = {}
+    for name in ("conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b", "convPa", "convPb", "convDa", "convDb"):
+        w, b = sp_sd[name + ".weight"].double(), sp_sd[name + ".bias"].double()
+        if name == "convPb":
+            w = torch.cat([w, torch.zeros(3, *w.shape[1:], dtype=w.dtype)])
+            b = torch.cat([b, torch.zeros(3, dtype=b.dtype)])
+        out[f"superpoint.{name}.weight"] = _khwc(w, pad_cin_to=4 if name == "conv1a" else 0)
+        out[f"superpoint.{name}.bias"] = b
+    n_kenc = 5
+    for i in range(n_kenc):
+        c = f"kenc.encoder.{3 * i}"
+        w, b = sg_sd[c + ".weight"][:, :, 0].double(), sg_sd[c + ".bias"].double()
+        if i < n_kenc - 1:
+            w, b = fold_batchnorm1d(w, b, sg_sd, f"kenc.encoder.{3 * i + 1}")
+        if i == 0:
+            w = torch.nn.functional.pad(w, (0, 1))
+        out[f"superglue.kenc.{i}.weight"], out[f"superglue.kenc.{i}.bias"] = w, b
+    perm = superglue_head_permutation()
+    l = 0
+    while f"gnn.layers.{l}.attn.merge.weight" in sg_sd:
+        p = f"gnn.layers.{l}"
+        ws = [sg_sd[f"{p}.attn.proj.{j}.weight"][:, :, 0].double()[perm] for j in range(3)]
+        bs = [sg_sd[f"{p}.attn.proj.{j}.bias"].double()[perm] for j in range(3)]
+        out[f"superglue.gnn.{l}.qkv.weight"], out[f"superglue.gnn.{l}.qkv.bias"] = torch.cat(ws), torch.cat(bs)
+        out[f"superglue.gnn.{l}.merge.weight"] = sg_sd[p + ".attn.merge.weight"][:, :, 0].double()[:, perm]
+        out[f"superglue.gnn.{l}.merge.bias"] = sg_sd[p + ".attn.merge.bias"].double()
+        w0, b0 = fold_batchnorm1d(sg_sd[p + ".mlp.0.weight"][:, :, 0], sg_sd[p + ".mlp.0.bias"], sg_sd, p + ".mlp.1")
+        out[f"superglue.gnn.{l}.mlp0.weight"], out[f"superglue.gnn.{l}.mlp0.bias"] = w0, b0
+        out[f"superglue.gnn.{l}.mlp1.weight"] = sg_sd[p + ".mlp.3.weight"][:, :, 0].double()
+        out[f"superglue.gnn.{l}.mlp1.bias"] = sg_sd[p + ".mlp.3.bias"].double()
+        l += 1
+    if l != 18:
+        raise ValueError(f"pack_superglue: the engine runs the 18 layers of ['self', 'cross'] * 9; the checkpoint has {l}")
+    out["superglue.final_proj.weight"] = sg_sd["final_proj.weight"][:, :, 0].double()
+    out["superglue.final_proj.bias"] = sg_sd["final_proj.bias"].double()
+    out["superglue.bin_score"] = sg_sd["bin_score"].double().reshape(1)
+    return {k: v.to(dtype).contiguous().to(device) for k, v in out.items()}
+
+
 def window_row_map(grid: int, window: int, batches: int, rows: int = 0) -> torch.Tensor:
     """Row map of SAM's window_partition (App. A-3): entry ((b*nwin + w)*window^2 + i) = source token row
     b*grid^2 + y*grid + x, or -1 where the window hangs over the zero padding.  `rows` > 0 (a multiple of `window`):

@@ -791,3 +791,237 @@ class RaftPointTracker(PointTracker):
             trajs.append(t)
             viss.append(v)
         return torch.stack(trajs), torch.stack(viss)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# SuperGlue (sam_pt/point_tracker/superglue/)
+# ------------------------------------------------------------------------------------------------------------------
+SUPERPOINT_DEFAULTS = {"descriptor_dim": 256, "nms_radius": 4, "keypoint_threshold": 0.005, "max_keypoints": -1,
+                       "remove_borders": 4}                                                  # superpoint.py:107-113
+SUPERGLUE_DEFAULTS = {"descriptor_dim": 256, "weights": "indoor", "keypoint_encoder": [32, 64, 128, 256],
+                      "GNN_layers": ["self", "cross"] * 9, "sinkhorn_iterations": 100, "match_threshold": 0.2}   # superglue.py:199-206
+
+
+def superglue_keypoint_capacity(H: int, W: int, nms_radius: int) -> int:
+    """Keypoints a frame can hold at most: survivors of simple_nms are at least ``nms_radius + 1`` pixels apart."""
+    s = int(nms_radius) + 1
+    return max(1, ((H + s - 1) // s) * ((W + s - 1) // s))
+
+
+def register_with_reference() -> bool:
+    """The reference's ``SamPt`` recognises the mask-consuming tracker by ``isinstance(self.point_tracker,
+    SuperGluePointTracker)`` against ITS class (sam_pt/modeling/sam_pt.py:189, :437).  That class is an ABC (``PointTracker``
+    is one), so ours is registered as a virtual subclass of it and passes that test.  Returns False where the reference
+    package is not importable (nothing to register with)."""
+    try:
+        from sam_pt.point_tracker.superglue.tracker import SuperGluePointTracker as Ref
+    except Exception:
+        return False
+    Ref.register(SuperGluePointTracker)
+    return True
+
+
+class SuperGluePointTracker(PointTracker):
+    """SuperPoint keypoints of frame 0 matched by SuperGlue to every later frame, independently per frame, behind the
+    constructor of ``sam_pt.point_tracker.superglue.SuperGluePointTracker`` (superglue/tracker.py:24-61;
+    configs/model/point_tracker/superglue.yaml).  The only tracker that needs ``set_masks`` before ``forward``.
+
+    The whole clip runs on the device (csrc/engine_superglue.hip, csrc/superglue.hip): SuperPoint once per frame, SuperGlue
+    per pair, and the tracker's per-mask split of the matched points.  The random draws stay on the host, in the
+    reference's order and with its arguments (``np.random.choice(a=len, size=min(len, k))``, per frame, per mask,
+    positives then negatives), so a seeded run consumes NumPy's global generator identically.  Host synchronisations per
+    clip: the keypoint counts and the selection counts — two, whatever T is.
+
+    ``matching_config[...]['checkpoint']`` absent or None: seeded random weights (``seed``).  Refused by name:
+    ``resize`` other than "no resize" (the reference raises on it as well), ``max_keypoints`` other than -1, and network
+    shapes other than the shipped ones."""
+
+    def __init__(self, positive_points_per_mask: int, negative_points_per_mask: int, resize, matching_config,
+                 seed: int = 72, keypoint_capacity: Optional[int] = None,
+                 state_dicts: Optional[Tuple[Dict[str, torch.Tensor], Dict[str, torch.Tensor]]] = None):
+        super().__init__()
+        self.positive_points_per_mask = int(positive_points_per_mask)
+        self.negative_points_per_mask = int(negative_points_per_mask)
+        if self.positive_points_per_mask < 0 or self.negative_points_per_mask < 0 or \
+                self.positive_points_per_mask + self.negative_points_per_mask < 1:
+            raise ValueError("SuperGluePointTracker: needs at least one point per mask")
+        resize = [int(v) for v in resize]
+        if len(resize) == 2 and resize[1] == -1:
+            resize = resize[0:1]
+        if len(resize) > 2 or len(resize) == 0:
+            raise ValueError("SuperGluePointTracker: Cannot specify more than two integers for `resize`")
+        if len(resize) == 2 or resize[0] > 0:
+            raise NotImplementedError(f"SuperGluePointTracker: resize={resize} is not supported: the reference's resize path "
+                                      "raises NotImplementedError as well (superglue/tracker.py:91-97); use resize=[-1, -1]")
+        self.resize = resize
+        cfg = {k: dict(v) for k, v in dict(matching_config).items()}
+        self.matching_config = cfg
+        sp = {**SUPERPOINT_DEFAULTS, **cfg.get("superpoint", {})}
+        sg = {**SUPERGLUE_DEFAULTS, **cfg.get("superglue", {})}
+        if int(sp["max_keypoints"]) != -1:
+            raise NotImplementedError(f"SuperGluePointTracker: max_keypoints={sp['max_keypoints']} is not supported (top-k "
+                                      "selection is not built); the shipped value is -1")
+        if int(sp["descriptor_dim"]) != 256 or int(sg["descriptor_dim"]) != 256:
+            raise NotImplementedError("SuperGluePointTracker: descriptor_dim must be 256")
+        if list(sg["keypoint_encoder"]) != SUPERGLUE_DEFAULTS["keypoint_encoder"] or list(sg["GNN_layers"]) != SUPERGLUE_DEFAULTS["GNN_layers"]:
+            raise NotImplementedError("SuperGluePointTracker: keypoint_encoder / GNN_layers other than the shipped networks")
+        if int(sp["nms_radius"]) < 0 or int(sp["nms_radius"]) > 16:
+            raise NotImplementedError("SuperGluePointTracker: nms_radius must be within 0..16")
+        if int(sg["sinkhorn_iterations"]) < 0:
+            raise ValueError("SuperGluePointTracker: sinkhorn_iterations must not be negative")
+        self.sp_cfg, self.sg_cfg = sp, sg
+        from .weights import init_superglue_state_dict, init_superpoint_state_dict
+        if state_dicts is not None:
+            self._sp_sd, self._sg_sd = state_dicts
+        else:
+            a, b = sp.get("checkpoint"), sg.get("checkpoint")
+            self._sp_sd = torch.load(a, map_location="cpu") if a is not None else init_superpoint_state_dict(seed)
+            self._sg_sd = torch.load(b, map_location="cpu") if b is not None else init_superglue_state_dict(seed)
+        self.keypoint_capacity = keypoint_capacity
+        self.masks = None
+        self._h = None
+        self._device = None
+        self.stats = {"frames": 0, "pairs": 0, "host_syncs": 0, "keypoints": []}
+
+    def _ensure(self, device: torch.device):
+        if self._h is not None and self._device == device:
+            return
+        _lib.require_hip(device, "SuperGluePointTracker")
+        from .pack import pack_superglue
+        lib = _lib.load()
+        self._w = pack_superglue(self._sp_sd, self._sg_sd, device)
+        names, ptrs, n = _lib.name_table(self._w)
+        h = C.c_void_p()
+        _lib.check(lib.sampt_sg_create(names, ptrs, n, C.byref(h)), "sampt_sg_create")
+        self._h, self._device, self._lib = h, device, lib
+
+    def __del__(self):
+        if getattr(self, "_h", None) is not None:
+            try:
+                self._lib.sampt_sg_destroy(self._h)
+            except Exception:
+                pass
+
+    def set_masks(self, masks):
+        """masks (n_masks, H, W) with values in {0, 1}: the query masks of the clip's first frame, at the frames' own size."""
+        masks = torch.as_tensor(masks)
+        if masks.dim() != 3:
+            raise ValueError("SuperGluePointTracker.set_masks: masks must be (n_masks, height, width)")
+        self.masks = masks
+
+    @torch.no_grad()
+    @_lib.on_device(lambda self, frames, *a, **k: frames.device)
+    def detect(self, frames: torch.Tensor, return_dense: bool = False):
+        """frames (T,3,H,W) uint8 on the device -> dict(kpts (T,cap,2), scores (T,cap), desc (T,cap,256), counts list[int],
+        [dense (T,Hs,Ws)]); one host synchronisation.  More keypoints than the capacity raise (nothing is truncated)."""
+        assert frames.dtype == torch.uint8 and frames.dim() == 4, "frames must be uint8 (T,3,H,W)"
+        T, _, H, W = frames.shape
+        if H < 8 or W < 8:
+            raise ValueError("SuperGluePointTracker: frames must be at least 8 x 8 pixels")
+        dev = frames.device
+        self._ensure(dev)
+        r = int(self.sp_cfg["nms_radius"])
+        cap = int(self.keypoint_capacity) if self.keypoint_capacity else superglue_keypoint_capacity(H, W, r)
+        kpts = torch.empty((T, cap, 2), dtype=torch.float32, device=dev)
+        scores = torch.empty((T, cap), dtype=torch.float32, device=dev)
+        desc = torch.empty((T, cap, 256), dtype=torch.float32, device=dev)
+        counts = torch.empty((T,), dtype=torch.int32, device=dev)
+        dense = torch.empty((T, H // 8 * 8, W // 8 * 8), dtype=torch.float32, device=dev) if return_dense else None
+        host = (C.c_int * T)()
+        nbytes = C.c_size_t()
+        _lib.check(self._lib.sampt_sg_workspace_bytes(self._h, T, H, W, 0, 0, C.byref(nbytes), None), "sampt_sg_workspace_bytes")
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        _lib.check(self._lib.sampt_sg_detect(self._h, _lib.ptr(frames.contiguous()), T, H, W, r, float(self.sp_cfg["keypoint_threshold"]),
+                                             int(self.sp_cfg["remove_borders"]), cap, _lib.ptr(kpts), _lib.ptr(scores), _lib.ptr(desc),
+                                             _lib.ptr(counts), host, _lib.ptr(dense), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                   "sampt_sg_detect")
+        self.stats["frames"] += T
+        self.stats["host_syncs"] += 1
+        out = {"kpts": kpts, "scores": scores, "desc": desc, "counts": [int(c) for c in host], "counts_dev": counts, "cap": cap,
+               "hw": (H, W)}
+        self.stats["keypoints"] = out["counts"]
+        if return_dense:
+            out["dense"] = dense
+        return out
+
+    def match_workspace(self, det):
+        n0, n1 = det["counts"][0], max(det["counts"][1:], default=0)
+        nbytes = C.c_size_t()
+        _lib.check(self._lib.sampt_sg_workspace_bytes(self._h, 1, det["hw"][0], det["hw"][1], n0, n1, None, C.byref(nbytes)),
+                   "sampt_sg_workspace_bytes")
+        return torch.empty(max(nbytes.value, 256), dtype=torch.uint8, device=det["kpts"].device)
+
+    @torch.no_grad()
+    @_lib.on_device(lambda self, det, *a, **k: det["kpts"].device)
+    def match(self, det, i: int, ws: Optional[torch.Tensor] = None, debug: bool = False):
+        """SuperGlue between frame 0 and frame i of ``detect``'s result -> (matches0 int32 (n0,), matching_scores0 (n0,)) on the
+        device, no host synchronisation.  ``debug`` adds the GNN output descriptors (n0 + n1, 256), the score matrix (n0, n1)
+        and Sinkhorn's u | v."""
+        dev = det["kpts"].device
+        n0, n1 = det["counts"][0], det["counts"][i]
+        H, W = det["hw"]
+        ws = ws if ws is not None else self.match_workspace(det)
+        m0 = torch.empty((n0,), dtype=torch.int32, device=dev)
+        s0 = torch.empty((n0,), dtype=torch.float32, device=dev)
+        both = n0 > 0 and n1 > 0
+        gnn = torch.empty((n0 + n1, 256), dtype=torch.float32, device=dev) if debug and both else None
+        sm = torch.empty((n0, n1), dtype=torch.float32, device=dev) if debug and both else None
+        uv = torch.empty((n0 + n1 + 2,), dtype=torch.float32, device=dev) if debug and both else None
+        _lib.check(self._lib.sampt_sg_match(self._h, _lib.ptr(det["kpts"][0]), _lib.ptr(det["scores"][0]), _lib.ptr(det["desc"][0]), n0,
+                                            _lib.ptr(det["kpts"][i]), _lib.ptr(det["scores"][i]), _lib.ptr(det["desc"][i]), n1, H, W,
+                                            int(self.sg_cfg["sinkhorn_iterations"]), float(self.sg_cfg["match_threshold"]),
+                                            _lib.ptr(m0) if n0 else None, _lib.ptr(s0) if n0 else None, _lib.ptr(gnn), _lib.ptr(sm),
+                                            _lib.ptr(uv), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "sampt_sg_match")
+        self.stats["pairs"] += 1
+        return (m0, s0, gnn, sm, uv) if debug else (m0, s0)
+
+    @torch.no_grad()
+    @_lib.on_device(lambda self, rgbs, query_points: rgbs.device)
+    def forward(self, rgbs, query_points):
+        assert self.masks is not None, "Masks must be set before calling forward() for SuperGluePointTracker"
+        assert rgbs.dtype == torch.uint8, "rgbs must be uint8 (PointTracker.forward contract)"
+        import numpy as np
+        B, T, _, H, W = rgbs.shape
+        if B != 1:
+            raise NotImplementedError("Batch size > 1 is not supported for SuperGluePointTracker yet")
+        dev = rgbs.device
+        _lib.require_hip(dev, "SuperGluePointTracker")
+        n_pos, n_neg = self.positive_points_per_mask, self.negative_points_per_mask
+        P = n_pos + n_neg
+        nm = self.masks.shape[0]
+        assert P * nm == query_points.shape[1]
+        if tuple(self.masks.shape[1:]) != (H, W):
+            raise ValueError(f"SuperGluePointTracker: masks of {tuple(self.masks.shape[1:])} for frames of {(H, W)}")
+        masks = self.masks.to(device=dev, dtype=torch.float32).contiguous()
+        det = self.detect(rgbs[0])
+        n0 = det["counts"][0]
+        lcap = max(1, n0)
+        traj = torch.empty((T, nm * P, 2), dtype=torch.float32, device=dev)
+        vis = torch.empty((T, nm * P), dtype=torch.float32, device=dev)
+        qxy = query_points[0, :, 1:].to(device=dev, dtype=torch.float32).contiguous()
+        lists = counts = draw = None
+        if T > 1:
+            lists = torch.empty((T - 1, nm, 2, lcap), dtype=torch.int32, device=dev)
+            counts = torch.zeros((T - 1, nm, 2), dtype=torch.int32, device=dev)
+            ws = self.match_workspace(det)
+            for i in range(1, T):
+                m0, _ = self.match(det, i, ws)
+                if n0 > 0 and det["counts"][i] > 0:
+                    _lib.check(self._lib.sampt_sg_select(_lib.ptr(m0), n0, _lib.ptr(det["kpts"][i]), _lib.ptr(masks), nm, H, W, lcap,
+                                                         _lib.ptr(lists[i - 1]), _lib.ptr(counts[i - 1]), _lib.stream_ptr()),
+                               "sampt_sg_select")
+            host = counts.cpu().numpy()                         # the clip's second (and last) host synchronisation
+            self.stats["host_syncs"] += 1
+            pick = np.full((T - 1, nm, P), -1, dtype=np.int32)
+            for i in range(T - 1):                              # tracker.py:137-162: per frame, per mask, positives then negatives
+                for mi in range(nm):
+                    for which, want, off in ((0, n_pos, 0), (1, n_neg, n_pos)):
+                        have = int(host[i, mi, which])
+                        idx = np.random.choice(a=have, size=min(have, want))
+                        pick[i, mi, off:off + len(idx)] = idx
+            draw = torch.from_numpy(pick).to(dev)
+        _lib.check(self._lib.sampt_sg_gather(_lib.ptr(qxy), _lib.ptr(det["kpts"]), det["cap"], _lib.ptr(lists), lcap, _lib.ptr(counts),
+                                             _lib.ptr(draw), T, nm, n_pos, n_neg, _lib.ptr(traj), _lib.ptr(vis), _lib.stream_ptr()),
+                   "sampt_sg_gather")
+        self.masks = None                                       # tracker.py:188-189: used up
+        return traj[None], vis[None]

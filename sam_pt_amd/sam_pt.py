@@ -242,7 +242,9 @@ class SamPt(nn.Module):
             # tracker's latency-bound window rounds (one host sync each) run beside the SAM encoder on a high-priority
             # side stream, and the decoder chain runs on a third stream once the trajectories are on the host and the
             # encoder is done (see the knobs in __init__ for the measured alternatives).
-            overlap = (not self.use_point_reinit) and images.is_cuda and self.overlap_tracker_and_encoder
+            # (a tracker that consumes the query masks — SuperGlue — cannot start before they exist: it runs after the encoder)
+            overlap = (not self.use_point_reinit) and images.is_cuda and self.overlap_tracker_and_encoder \
+                and not hasattr(self.point_tracker, "set_masks")
             pipeline = None
             self._mark("start")
             if overlap:
@@ -316,6 +318,13 @@ class SamPt(nn.Module):
             if not fused or self.compute_unused_query_masks or hasattr(self.point_tracker, "set_masks"):
                 query_masks = self.extract_query_masks(images, query_points, feats)
         assert query_masks is None or query_masks.shape == (n_masks, height, width)
+        if hasattr(self.point_tracker, "set_masks"):
+            # The SuperGlue point tracker matches keypoints and needs the query masks (sam_pt.py:188-191).  With point
+            # re-initialisation every window sets its own masks before it tracks (_forward_w_reinit_inner), so the masks the
+            # reference also sets here are replaced before any use: they are not set, and the tracker sees one call per window.
+            assert self.point_tracker_mask_batch_size >= n_masks
+            if not self.use_point_reinit:
+                self.point_tracker.set_masks(query_masks)
         target_hw = tuple(video["target_hw"])
 
         def tail(trajectories, visibilities, logits, scores, scores_per_frame):
@@ -438,6 +447,11 @@ class SamPt(nn.Module):
             q_i = current[tracked].clone()
             q_i[:, :, 0] -= start
             assert (q_i[:, :, 0] == 0).all()
+            if hasattr(self.point_tracker, "set_masks"):
+                # the mask-consuming tracker gets the query masks of the window's first frame (sam_pt.py:436-440)
+                q_masks_i = self.extract_query_masks(images[start:end_trk], q_i, feats[start:end_trk] if feats is not None else None)
+                assert self.point_tracker_mask_batch_size >= n_masks
+                self.point_tracker.set_masks(q_masks_i)
             traj_i, vis_i = self._track_points(images[start:end_trk], q_i)
             traj_i, vis_i = traj_i[:H], vis_i[:H]
             _, logits_i, spf_i = self._apply_sam_to_trajectories(images[start:end], traj_i, vis_i,

@@ -427,3 +427,81 @@ def init_sam_state_dict(cfg: SamConfig, seed: int = 72, hq: bool = False) -> "Or
         w.norm(M + "embedding_maskfeature.1", C // 4)
         w.conv(M + "embedding_maskfeature.3", C // 8, C // 4, 3, 3)
     return w.sd
+
+
+# --------------------------------------------------------------------------------------
+# SuperPoint + SuperGlue (sam_pt/point_tracker/superglue/models/{superpoint,superglue}.py)
+# --------------------------------------------------------------------------------------
+SUPERGLUE_KENC_DIMS = (3, 32, 64, 128, 256, 256)
+SUPERGLUE_GNN_LAYERS = 18
+SUPERGLUE_HEADS = 4
+
+
+def init_superpoint_state_dict(seed: int = 72) -> "OrderedDict[str, torch.Tensor]":
+    """Random SuperPoint weights under the key names of ``superpoint_v1.pth`` (superpoint.py:123-138): eight 3 x 3
+    convolutions of the shared encoder, the detector head (convPa, convPb -> 65) and the descriptor head (convDa, convDb).
+
+    Kaiming (fan-in, ReLU) weights keep the activations' scale through the eight layers; the detector's last layer is
+    scaled by 1.25 so that the softmax over the 65 channels is uneven enough for the local maxima of the score map to lie on
+    both sides of the shipped ``keypoint_threshold`` of 0.005 while no score reaches 0.5 (figures: DESIGN.md §4)."""
+    w = _Init(seed)
+    c1, c2, c3, c4, c5 = 64, 64, 128, 128, 256
+    for name, cout, cin, k in (("conv1a", c1, 1, 3), ("conv1b", c1, c1, 3), ("conv2a", c2, c1, 3), ("conv2b", c2, c2, 3),
+                               ("conv3a", c3, c2, 3), ("conv3b", c3, c3, 3), ("conv4a", c4, c3, 3), ("conv4b", c4, c4, 3),
+                               ("convPa", c5, c4, 3), ("convPb", 65, c5, 1), ("convDa", c5, c4, 3), ("convDb", 256, c5, 1)):
+        w.normal(name + ".weight", (cout, cin, k, k), math.sqrt(2.0 / (cin * k * k)))
+        w.uniform(name + ".bias", (cout,), 0.1)
+    w.sd["convPb.weight"] = w.sd["convPb.weight"] * 1.25
+    return w.sd
+
+
+def init_superglue_state_dict(seed: int = 72, gnn_scale: float = 0.1, proj_gain: float = 40.0,
+                              bin_score: float = 125.0) -> "OrderedDict[str, torch.Tensor]":
+    """Random SuperGlue weights under the key names of ``superglue_outdoor.pth`` (superglue.py:208-223): ``kenc.encoder``
+    (Conv1d / BatchNorm1d / ReLU x 4, Conv1d), 18 x ``gnn.layers.<l>.{attn.proj.<0..2>, attn.merge, mlp.<0, 1, 3>}``,
+    ``final_proj`` and ``bin_score``.  Every BatchNorm1d gets non-trivial running statistics and affine terms, so that
+    folding them (pack.pack_superglue) is exercised.
+
+    DAMPED init, as for CoTracker's flow head: with PyTorch's default init the 18 residual layers swamp the unit-norm
+    SuperPoint descriptors, the rows of the score matrix differ mostly by their norms and almost nothing passes the
+    mutual check.  The last convolution of every layer's MLP and of the keypoint encoder is therefore scaled by
+    ``gnn_scale``: the residual stream stays dominated by the descriptors while every layer still contributes.
+    ``final_proj`` is a random projection of gain ``proj_gain`` (scores of about ``proj_gain ** 2 / 16``, peaked enough
+    for assignments above the shipped ``match_threshold`` of 0.2) and ``bin_score`` sits at the median score, where the
+    golden clip yields about 30 matches, 175 unmatched keypoints, mutual-check failures and matching scores on both sides
+    of the threshold (figures: DESIGN.md §4)."""
+    w = _Init(seed)
+
+    def bn(prefix, dim):
+        w.normal(prefix + ".weight", (dim,), 0.1, mean=1.0)
+        w.normal(prefix + ".bias", (dim,), 0.1)
+        w.normal(prefix + ".running_mean", (dim,), 0.2)
+        w.uniform(prefix + ".running_var", (dim,), 0.5)
+        w.sd[prefix + ".running_var"] = w.sd[prefix + ".running_var"] + 1.0          # in [0.5, 1.5]
+        w.sd[prefix + ".num_batches_tracked"] = torch.tensor(1000, dtype=torch.long)
+
+    def conv1d(prefix, cout, cin, gain=1.0, zero_bias=False):
+        b = 1.0 / math.sqrt(cin)
+        w.uniform(prefix + ".weight", (cout, cin, 1), b * gain)
+        w.uniform(prefix + ".bias", (cout,), b * gain)
+        if zero_bias:                                                                # nn.init.constant_(..., 0.0)
+            w.sd[prefix + ".bias"] = torch.zeros(cout)
+
+    d = SUPERGLUE_KENC_DIMS
+    for i in range(1, len(d)):
+        last = i == len(d) - 1
+        conv1d(f"kenc.encoder.{3 * (i - 1)}", d[i], d[i - 1], gain=gnn_scale if last else 1.0, zero_bias=last)
+        if not last:
+            bn(f"kenc.encoder.{3 * (i - 1) + 1}", d[i])
+    for l in range(SUPERGLUE_GNN_LAYERS):
+        p = f"gnn.layers.{l}"
+        conv1d(p + ".attn.merge", 256, 256)
+        for j in range(3):
+            conv1d(f"{p}.attn.proj.{j}", 256, 256, gain=2.0 if j < 2 else 1.0)
+        conv1d(p + ".mlp.0", 512, 512)
+        bn(p + ".mlp.1", 512)
+        conv1d(p + ".mlp.3", 256, 512, gain=gnn_scale, zero_bias=True)
+    w.normal("final_proj.weight", (256, 256, 1), proj_gain / 16.0)
+    w.uniform("final_proj.bias", (256,), 0.05)
+    w.sd["bin_score"] = torch.tensor(float(bin_score))
+    return w.sd
