@@ -516,6 +516,23 @@ int sampt_jf_counts(const void* seg_dev, int seg_kind, float seg_thr, const int3
                     const void* ann_dev, int ann_kind, float ann_thr, const int32_t* ann_values_dev, const int32_t* ann_planes_dev,
                     const uint8_t* void_dev, const int32_t* void_planes_dev, int n, int h, int w, int radius,
                     int32_t* counts_out_dev, void* workspace_dev, size_t workspace_bytes, sampt_stream_t stream);
+/* The J / F counts of every (seg mask p, ann mask k) pair of every frame (csrc/vos_pairs.hip): what the DAVIS unsupervised protocol needs
+ * before its assignment.  Every mask is read once and its boundary dilated once, whatever the number of its partners; the pair pass is
+ * a popcount GEMM over bit words.  The two sources are described as for sampt_jf_counts (kind, threshold, values_dev, planes_dev, now
+ * int32 [n_frames * n_seg] and [n_frames * n_ann]); seg mask (p, t) is item t * n_seg + p, ann mask (k, t) item t * n_ann + k.
+ * void_dev: optional bytes, one plane per frame (void_planes_dev int32 [n_frames] or NULL: frame t reads plane t), cleared from both
+ * sides.  Boundary map, disk, 0 <= radius <= 64 and "outside the image is 0" are those of sampt_jf_counts.  Outputs, int32:
+ *   pair_out_dev [n_frames][n_seg][n_ann][3] = inter, seg_match = |B(seg) & dil(B(ann))|, ann_match = |B(ann) & dil(B(seg))|;
+ *   seg_stat_out_dev [n_frames][n_seg][2] and ann_stat_out_dev [n_frames][n_ann][2] = area, |B|  (union = area + area - inter).
+ * The workspace (16-byte aligned, sampt_jf_pairs_workspace_bytes = 3 bits per pixel of every mask, rounded up to 64 rows; 0 for a bad
+ * shape or radius) holds the mask, boundary and dilated-boundary bit-planes.  Integer sums: bitwise repeatable.  With too small a
+ * workspace the call fails with SAMPT_ERR_WORKSPACE and the caller splits by frames.  3 * n_seg * n_ann * n_frames < 2^31. */
+size_t sampt_jf_pairs_workspace_bytes(int n_seg, int n_ann, int n_frames, int h, int w, int radius);
+int sampt_jf_pairs_counts(const void* seg_dev, int seg_kind, float seg_thr, const int32_t* seg_values_dev, const int32_t* seg_planes_dev,
+                          int n_seg, const void* ann_dev, int ann_kind, float ann_thr, const int32_t* ann_values_dev,
+                          const int32_t* ann_planes_dev, int n_ann, const uint8_t* void_dev, const int32_t* void_planes_dev, int n_frames,
+                          int h, int w, int radius, int32_t* pair_out_dev, int32_t* seg_stat_out_dev, int32_t* ann_stat_out_dev,
+                          void* workspace_dev, size_t workspace_bytes, sampt_stream_t stream);
 /* YouTube-VIS AP / AR on the device (csrc/vis_eval.hip): bit-planes of mask stacks, spatio-temporal intersection / union of all
  * (detection, ground truth) pairs of a video, and the greedy matching of the reference's YTVOSeval.evaluateVid.  Integer work and
  * one IEEE float64 division per IoU: bitwise repeatable and equal to the host restatement of sam_pt_amd/vis_metrics.py.

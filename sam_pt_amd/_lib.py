@@ -119,6 +119,9 @@ _SIGS = {
     "sampt_jf_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "sampt_jf_counts": (c_int, [_P, c_int, c_float, _P, _P, _P, c_int, c_float, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P,
                                 c_size_t, _P]),
+    "sampt_jf_pairs_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "sampt_jf_pairs_counts": (c_int, [_P, c_int, c_float, _P, _P, c_int, _P, c_int, c_float, _P, _P, c_int, _P, _P, c_int, c_int, c_int,
+                                      c_int, _P, _P, _P, _P, c_size_t, _P]),
     "sampt_bits_pack": (c_int, [_P, c_int, c_float, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "sampt_rle_decode_workspace_bytes": (c_size_t, [C.c_int64]),
     "sampt_rle_decode_bits": (c_int, [_P, _P, c_int, C.c_int64, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),

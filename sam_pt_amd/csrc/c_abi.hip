@@ -954,6 +954,29 @@ int sampt_jf_counts(const void* seg, int seg_kind, float seg_thr, const int32_t*
   return rc;
 }
 
+size_t sampt_jf_pairs_workspace_bytes(int n_seg, int n_ann, int n_frames, int h, int w, int radius) {
+  return jf_pairs_workspace_bytes(n_seg, n_ann, n_frames, h, w, radius);
+}
+
+int sampt_jf_pairs_counts(const void* seg, int seg_kind, float seg_thr, const int32_t* seg_values, const int32_t* seg_planes, int n_seg,
+                          const void* ann, int ann_kind, float ann_thr, const int32_t* ann_values, const int32_t* ann_planes, int n_ann,
+                          const uint8_t* void_px, const int32_t* void_planes, int n_frames, int h, int w, int radius, int32_t* pair_out,
+                          int32_t* seg_stat, int32_t* ann_stat, void* ws, size_t ws_bytes, sampt_stream_t stream) {
+  if (n_seg <= 0 || n_ann <= 0 || n_frames <= 0 || h <= 0 || w <= 0)
+    return fail(SAMPT_ERR_ARG, "sampt_jf_pairs_counts: bad shape (n_seg, n_ann, n_frames, h and w must be positive)");
+  if ((long)h * w >= (1L << 31)) return fail(SAMPT_ERR_ARG, "sampt_jf_pairs_counts: h * w must be below 2^31");
+  if (radius < 0 || radius > 64) return fail(SAMPT_ERR_ARG, "sampt_jf_pairs_counts: radius must be in 0 .. 64");
+  if (seg_kind < 0 || seg_kind > 2 || ann_kind < 0 || ann_kind > 2)
+    return fail(SAMPT_ERR_ARG, "sampt_jf_pairs_counts: unknown kind (0 = bytes, 1 = f32 with a threshold, 2 = uint8 index map)");
+  int rc = jf_pairs_counts(seg, seg_kind, seg_thr, (const int*)seg_values, (const int*)seg_planes, n_seg, ann, ann_kind, ann_thr,
+                           (const int*)ann_values, (const int*)ann_planes, n_ann, void_px, (const int*)void_planes, n_frames, h, w, radius,
+                           (int*)pair_out, (int*)seg_stat, (int*)ann_stat, ws, ws_bytes, (hipStream_t)stream);
+  if (rc == SAMPT_ERR_WORKSPACE) return fail(rc, "sampt_jf_pairs_counts: workspace too small for n_frames frames (split the stack by frames)");
+  if (rc == SAMPT_ERR_ARG)
+    return fail(rc, "sampt_jf_pairs_counts: null or misaligned pointer (an index map needs its values), or 3 * n_seg * n_ann * n_frames >= 2^31");
+  return rc;
+}
+
 int sampt_sam_track_decode(sampt_dec_t h, int frames, const float* features, const float* hq_features,
                            const float* pts, const int32_t* labels, int k, const int32_t* k_item,
                            const int32_t* npos_item, int ld_pts, int n_pos_first, int refine_iters, float iou_thr,

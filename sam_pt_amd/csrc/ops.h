@@ -335,6 +335,15 @@ size_t jf_workspace_bytes(int n, int h, int w, int radius);
 int jf_counts(const void* seg, int seg_kind, float seg_thr, const int* seg_values, const int* seg_planes, const void* ann, int ann_kind,
               float ann_thr, const int* ann_values, const int* ann_planes, const unsigned char* void_px, const int* void_planes, int n,
               int h, int w, int radius, int* counts, void* ws, size_t ws_bytes, hipStream_t s);
+// ---- vos_pairs.hip: the counts of J and F of every (seg mask p, ann mask k) pair of every frame.  Sources as for jf_counts; seg mask
+// (p, t) is item t * n_seg + p, ann mask (k, t) item t * n_ann + k; void_px: one optional byte plane per frame.  pair_out int32
+// [n_frames][n_seg][n_ann][3] = inter, seg_match, ann_match; seg_stat [n_frames][n_seg][2] and ann_stat [n_frames][n_ann][2] = area,
+// boundary count.  ws of jf_pairs_workspace_bytes (16-byte aligned) holds the mask, boundary and dilated-boundary bit-planes.
+size_t jf_pairs_workspace_bytes(int n_seg, int n_ann, int n_frames, int h, int w, int radius);
+int jf_pairs_counts(const void* seg, int seg_kind, float seg_thr, const int* seg_values, const int* seg_planes, int n_seg, const void* ann,
+                    int ann_kind, float ann_thr, const int* ann_values, const int* ann_planes, int n_ann, const unsigned char* void_px,
+                    const int* void_planes, int n_frames, int h, int w, int radius, int* pair_out, int* seg_stat, int* ann_stat, void* ws,
+                    size_t ws_bytes, hipStream_t s);
 // ---- vis_eval.hip: YouTube-VIS AP / AR.  Bit-planes: a stack [n][h][w] as uint64 [n][ceil(h / 64)][w], bit j of word (band b, column x)
 // = pixel (64 b + j, x), bits of rows >= h are 0.  pack: the three kinds of jf_counts -> bit-planes + area int32 [n].  rle_decode_bits:
 // the inverse of rle_count / rle_emit (status 0 = good; a bad mask's plane is zeros).  seq_iou_counts: int64 [D][G][2] = (inter, union)
