@@ -125,6 +125,8 @@ int sampt_pips2_update_f32(sampt_pips2_t h, const float* const pyr_dev[4], int H
  * (sam_pt_amd/pack.py::pack_cotracker).
  *   resize_frames_f32 : the adapter's F.interpolate(rgbs, interp_shape, mode="bilinear") (tracker.py:90-92) over `planes`
  *                       = T*3 single-channel planes, uint8 (src_u8 != 0) or float32 input, float32 output in [0, 255].
+ *                       Source positions are exact integer fractions (not torch's f32 product); every size <= 16384.  Also the
+ *                       entry point of the resize_planes kernel test.
  *   fnet_f32          : CoTracker.fnet (the BasicEncoder of PIPS, stride 4) on every float frame + the 4-level average-pool
  *                       pyramid of CorrBlock; each frame once per clip (InstanceNorm is per-sample), both directions share it.
  *   track_f32         : one CoTracker.forward (one temporal direction) over T >= 8 model frames: sliding windows of 8 frames
@@ -676,6 +678,62 @@ int sampt_avgpool2x2_nhwc(const float* src_dev, int n, int h, int w, int C, floa
  * ffeats_dev [n][S][128]; coords_dev [S][n][2] (level-0 feature-map pixels); out_dev [n][S][196]. */
 int sampt_corr_sample_f32(const float* const pyr_dev[4], int H0, int W0, const int32_t* frame_idx_dev, int S, int n,
                           const float* ffeats_dev, const float* coords_dev, float* out_dev, sampt_stream_t stream);
+/* The trackers' window kernels one by one (csrc/pips.hip, pips2.hip, cotracker.hip; layouts in those files' headers), exported for
+ * tests/test_gpu_tracker_kernels.py.  Every one returns SAMPT_ERR_ARG for a null pointer or a non-positive count before any launch.
+ * corr_sample_ex: sampt_corr_sample_f32 writing columns [xoff, xoff + 196) of rows of ldx floats; times (device [S], may be NULL)
+ *   additionally writes the rest of the PIPS mixer input (needs xoff == 128, 519 <= ldx <= 580), as build_input does. */
+int sampt_pips_corr_sample_ex(const float* const pyr[4], int H0, int W0, const int32_t* frame_idx, int S, int n, const float* ffeats,
+                              const float* coords, float* x, int ldx, int xoff, const float* times, sampt_stream_t stream);
+/* x [n][S][ldx]: columns [0, 128) = ffeats, [324, 519) = sin/cos embedding of (flow, time) and the three values, [519, ldx) = 0 */
+int sampt_pips_build_input_f32(const float* ffeats, const float* coords, const float* times, int S, int n, float* x, int ldx,
+                               sampt_stream_t stream);
+/* coords [S][n][2] = coords0 [n][2] = xys / stride; ffeats [n][S][128] = feat_init [n][128] on every frame */
+int sampt_pips_init_state_f32(const float* xys, const float* feat_init, float stride, int S, int n, float* coords, float* coords0,
+                              float* ffeats, sampt_stream_t stream);
+/* delta [n][S][130] = (dx, dy, 128 feature deltas): ffeats += gelu(Linear(GroupNorm(1, 128)(delta[2:]))), coords += delta[:2];
+ * coords0 (may be NULL) locks frame 0 to it.  up_wT: the Linear weight transposed to [in][out]. */
+int sampt_pips_apply_update_f32(const float* delta, const float* gn_w, const float* gn_b, const float* up_wT, const float* up_b,
+                                float* ffeats, float* coords, const float* coords0, int S, int n, sampt_stream_t stream);
+/* vis [S][n] = sigmoid(<ffeats, vis_w> + vis_b); traj [S][n][2] = coords * stride */
+int sampt_pips_finalize_f32(const float* ffeats, const float* vis_w, const float* vis_b, const float* coords, float stride, int S,
+                            int n, float* traj, float* vis, sampt_stream_t stream);
+/* Bookkeeping of the chained PIPS windows: q [n][3] = (t, x, y); cur int32 [n]; traj [T][n][2]; vis [T][n]; flip bytes [n];
+ * fidx int32 [n][S]; xys [n][2]; xy_feat [n][2] and f0 int32 [n] come together or are both NULL; tr [S][n][2] and vi [S][n] are a
+ * window's results; n_active int32 [1]. */
+int sampt_pips_chain_init(const float* q, int n, int T, int32_t* cur, float* traj, float* vis, sampt_stream_t stream);
+int sampt_pips_round_begin(const int32_t* cur, const uint8_t* flip, const float* traj, int T, int n, int S, int32_t* fidx, float* xys,
+                           float* xy_feat, int32_t* f0, float stride, sampt_stream_t stream);
+int sampt_pips_round_end(int32_t* cur, const float* tr, const float* vi, int T, int n, int S, float thr0, float* traj, float* vis,
+                         int32_t* n_active, sampt_stream_t stream);
+/* PIPS++: trajs0 [S][n][2] px; fmap [frames][H][W][128]; frame_idx int32 [n][S]; coords [S][n][2]; bak [n][2]; templates f1 / f2 /
+ * f4 [n][S][128] (written only when have_init == 0); x [n][S][720]; omega [32]; delta [n][S][2]. */
+int sampt_pips2_init_f32(const float* trajs0, const float* fmap, int H, int W, const int32_t* frame_idx, float stride, int S, int n,
+                         int have_init, float* coords, float* bak, float* f1, float* f2, float* f4, sampt_stream_t stream);
+int sampt_pips2_templates_f32(const float* fmap, int H, int W, const int32_t* frame_idx, const float* coords, int S, int n, float* f2,
+                              float* f4, sampt_stream_t stream);
+int sampt_pips2_build_input_f32(const float* coords, const float* omega, int S, int n, float* x, int ldx, sampt_stream_t stream);
+/* y [n][S][C] = relu(InstanceNorm1d over S of x); y may be x */
+int sampt_instnorm1d_relu_f32(const float* x, float* y, int n, int S, int C, sampt_stream_t stream);
+/* out [rows][cout] += identity [rows][cin] placed at channel (cout - cin) / 2; relu != 0: max(., 0) of the sum */
+int sampt_add_chanpad_f32(float* out, const float* identity, long rows, int cin, int cout, int relu, sampt_stream_t stream);
+int sampt_pips2_apply_delta_f32(const float* delta, const float* bak, float stride, int S, int n, int last, float* coords, float* trajs,
+                                sampt_stream_t stream);
+/* CoTracker windows: qxy [n][2] px, qt int32 [n], frame_map int32 [T]; xy0 [n][2]; fidx_pt int32 [n]; traj_out [T][n_total][2];
+ * vis_out [T][n_total]; window state coords [S][na][2], visin / mask [S][na], fidx int32 [na][S], ffeats [na][S][128]; carries
+ * coords_prev [S][prev][2], vis_prev [S][prev] (needed when prev > 0); pos [na][E] from the tables pos_x [W][E / 2], pos_y [H][E / 2];
+ * x [na][S][456] with the correlation columns [130, 326) already in place; times [S][456]. */
+int sampt_cot_prepare(const float* qxy, const int32_t* qt, const int32_t* frame_map, float stride, int n, int T, float* xy0,
+                      int32_t* fidx_pt, float* traj_out, float* vis_out, sampt_stream_t stream);
+int sampt_cot_window_init(int ind, int S_local, int prev, int na, int S, const int32_t* qt, const float* xy0, const int32_t* frame_map,
+                          const float* coords_prev, const float* vis_prev, const float* feat_init, float* coords, float* visin,
+                          float* mask, int32_t* fidx, float* ffeats, sampt_stream_t stream);
+int sampt_cot_pos_embed_f32(const float* coords, const float* pos_x, const float* pos_y, int H, int W, int E, int na, float* pos,
+                            sampt_stream_t stream);
+int sampt_cot_build_input_f32(const float* ffeats, const float* coords, const float* visin, const float* mask, const float* pos,
+                              const float* times, int S, int na, float* x, sampt_stream_t stream);
+int sampt_cot_window_store_f32(const float* ffeats, const float* vis_w, const float* vis_b, const float* coords, float stride, int S,
+                               int na, int ind, int S_local, int n_total, float* coords_prev, float* vis_prev, float* traj_out,
+                               float* vis_out, sampt_stream_t stream);
 /* The two kernels of a fused MLP-Mixer block (csrc/pips_mixer.hip; pips.py:96-128), exported for the kernel tests.
  * mlp: part_dev[slice][nseq*8][512] = fc2 over the slice's hidden units of gelu(fc1(LayerNorm(x)) + b1); x_dev [nseq*8][512],
  *      w1 [2048][512], b1 [2048], w2 [512][2048]; slices = 8, 16 or 32 (what sampt_pips_set_mixer's workgroup target selects).

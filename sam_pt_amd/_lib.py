@@ -182,6 +182,25 @@ _SIGS = {
     "sampt_resize_bilinear_nhwc": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "sampt_avgpool2x2_nhwc": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "sampt_corr_sample_f32": (c_int, [C.POINTER(_P), c_int, c_int, _P, c_int, c_int, _P, _P, _P, _P]),
+    "sampt_pips_corr_sample_ex": (c_int, [C.POINTER(_P), c_int, c_int, _P, c_int, c_int, _P, _P, _P, c_int, c_int, _P, _P]),
+    "sampt_pips_build_input_f32": (c_int, [_P, _P, _P, c_int, c_int, _P, c_int, _P]),
+    "sampt_pips_init_state_f32": (c_int, [_P, _P, c_float, c_int, c_int, _P, _P, _P, _P]),
+    "sampt_pips_apply_update_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
+    "sampt_pips_finalize_f32": (c_int, [_P, _P, _P, _P, c_float, c_int, c_int, _P, _P, _P]),
+    "sampt_pips_chain_init": (c_int, [_P, c_int, c_int, _P, _P, _P, _P]),
+    "sampt_pips_round_begin": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_float, _P]),
+    "sampt_pips_round_end": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, _P, _P, _P, _P]),
+    "sampt_pips2_init_f32": (c_int, [_P, _P, c_int, c_int, _P, c_float, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    "sampt_pips2_templates_f32": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P]),
+    "sampt_pips2_build_input_f32": (c_int, [_P, _P, c_int, c_int, _P, c_int, _P]),
+    "sampt_instnorm1d_relu_f32": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "sampt_add_chanpad_f32": (c_int, [_P, _P, C.c_long, c_int, c_int, c_int, _P]),
+    "sampt_pips2_apply_delta_f32": (c_int, [_P, _P, c_float, c_int, c_int, c_int, _P, _P, _P]),
+    "sampt_cot_prepare": (c_int, [_P, _P, _P, c_float, c_int, c_int, _P, _P, _P, _P, _P]),
+    "sampt_cot_window_init": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "sampt_cot_pos_embed_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
+    "sampt_cot_build_input_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P]),
+    "sampt_cot_window_store_f32": (c_int, [_P, _P, _P, _P, c_float, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "sampt_attention_f32": (c_int, [c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "sampt_cotracker_attention_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "sampt_vit_attention_f16": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),

@@ -222,7 +222,7 @@ void sampt_cotracker_destroy(sampt_cotracker_t h) { delete h; }
 int sampt_resize_frames_f32(const void* frames, int src_u8, long planes, int H, int W, float* out, int out_h, int out_w,
                             sampt_stream_t stream) {
   if (!frames || !out || planes <= 0 || H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0)
-    return fail(SAMPT_ERR_ARG, "sampt_resize_frames_f32: bad arguments");
+    return fail(SAMPT_ERR_ARG, "sampt_resize_frames_f32: bad arguments (null pointer, a count <= 0 or a size above 16384)");
   return resize_planes(frames, src_u8, planes, H, W, out, out_h, out_w, (hipStream_t)stream);
 }
 
@@ -1269,6 +1269,145 @@ int sampt_index_masks(const float* logits, int M, long npix, uint8_t* out, sampt
 int sampt_corr_sample_f32(const float* const pyr[4], int H0, int W0, const int32_t* frame_idx, int S, int n,
                           const float* ffeats, const float* coords, float* out, sampt_stream_t stream) {
   return pips_corr_sample(make_pyr(pyr, H0, W0), frame_idx, S, n, 128, ffeats, coords, out, 196, 0, (hipStream_t)stream);
+}
+
+// Handle-free wrappers of the trackers' window kernels for the kernel tests (tests/test_gpu_tracker_kernels.py): every one refuses
+// null pointers and non-positive counts before any launch.
+int sampt_pips_corr_sample_ex(const float* const pyr[4], int H0, int W0, const int32_t* frame_idx, int S, int n, const float* ffeats,
+                              const float* coords, float* x, int ldx, int xoff, const float* times, sampt_stream_t stream) {
+  if (!pyr || !pyr[0] || !pyr[1] || !pyr[2] || !pyr[3] || !frame_idx || !ffeats || !coords || !x || S <= 0 || n <= 0 || H0 < 16 ||
+      W0 < 16 || xoff < 0 || ldx < xoff + 196)
+    return fail(SAMPT_ERR_ARG, "sampt_pips_corr_sample_ex: bad arguments (null pointer, S, n <= 0, H0, W0 < 16 or ldx < xoff + 196)");
+  if (times && (xoff != 128 || ldx < 519 || ldx > 580))
+    return fail(SAMPT_ERR_ARG, "sampt_pips_corr_sample_ex: the fused tail needs xoff == 128 and 519 <= ldx <= 580");
+  return pips_corr_sample(make_pyr(pyr, H0, W0), (const int*)frame_idx, S, n, 128, ffeats, coords, x, ldx, xoff, (hipStream_t)stream,
+                          times);
+}
+
+int sampt_pips_build_input_f32(const float* ffeats, const float* coords, const float* times, int S, int n, float* x, int ldx,
+                               sampt_stream_t stream) {
+  if (!ffeats || !coords || !times || !x || S <= 0 || n <= 0 || ldx < 519 || ldx > 580)
+    return fail(SAMPT_ERR_ARG, "sampt_pips_build_input_f32: bad arguments (null pointer, S, n <= 0 or ldx outside [519, 580])");
+  return pips_build_input(ffeats, coords, times, S, n, x, ldx, (hipStream_t)stream);
+}
+
+int sampt_pips_init_state_f32(const float* xys, const float* feat_init, float stride, int S, int n, float* coords, float* coords0,
+                              float* ffeats, sampt_stream_t stream) {
+  if (!xys || !feat_init || !coords || !coords0 || !ffeats || S <= 0 || n <= 0 || !(stride > 0.f))
+    return fail(SAMPT_ERR_ARG, "sampt_pips_init_state_f32: bad arguments");
+  return pips_init_state(xys, feat_init, stride, S, n, coords, coords0, ffeats, (hipStream_t)stream);
+}
+
+int sampt_pips_apply_update_f32(const float* delta, const float* gn_w, const float* gn_b, const float* up_wT, const float* up_b,
+                                float* ffeats, float* coords, const float* coords0, int S, int n, sampt_stream_t stream) {
+  if (!delta || !gn_w || !gn_b || !up_wT || !up_b || !ffeats || !coords || S <= 0 || n <= 0)
+    return fail(SAMPT_ERR_ARG, "sampt_pips_apply_update_f32: bad arguments");
+  return pips_update(delta, gn_w, gn_b, up_wT, up_b, ffeats, coords, coords0, S, n, (hipStream_t)stream);
+}
+
+int sampt_pips_finalize_f32(const float* ffeats, const float* vis_w, const float* vis_b, const float* coords, float stride, int S,
+                            int n, float* traj, float* vis, sampt_stream_t stream) {
+  if (!ffeats || !vis_w || !vis_b || !coords || !traj || !vis || S <= 0 || n <= 0)
+    return fail(SAMPT_ERR_ARG, "sampt_pips_finalize_f32: bad arguments");
+  return pips_finalize(ffeats, vis_w, vis_b, coords, stride, S, n, traj, vis, (hipStream_t)stream);
+}
+
+int sampt_pips_chain_init(const float* q, int n, int T, int32_t* cur, float* traj, float* vis, sampt_stream_t stream) {
+  if (!q || !cur || !traj || !vis || n <= 0 || T <= 0) return fail(SAMPT_ERR_ARG, "sampt_pips_chain_init: bad arguments");
+  return pips_chain_init(q, n, T, (int*)cur, traj, vis, (hipStream_t)stream);
+}
+
+int sampt_pips_round_begin(const int32_t* cur, const uint8_t* flip, const float* traj, int T, int n, int S, int32_t* fidx, float* xys,
+                           float* xy_feat, int32_t* f0, float stride, sampt_stream_t stream) {
+  if (!cur || !flip || !traj || !fidx || !xys || T <= 0 || n <= 0 || S <= 0 || !xy_feat != !f0 || (xy_feat && !(stride > 0.f)))
+    return fail(SAMPT_ERR_ARG, "sampt_pips_round_begin: bad arguments (xy_feat and f0 come together)");
+  return pips_round_begin((const int*)cur, flip, traj, T, n, S, (int*)fidx, xys, xy_feat, (int*)f0, stride, (hipStream_t)stream);
+}
+
+int sampt_pips_round_end(int32_t* cur, const float* tr, const float* vi, int T, int n, int S, float thr0, float* traj, float* vis,
+                         int32_t* n_active, sampt_stream_t stream) {
+  if (!cur || !tr || !vi || !traj || !vis || !n_active || T <= 0 || n <= 0 || S <= 0)
+    return fail(SAMPT_ERR_ARG, "sampt_pips_round_end: bad arguments");
+  return pips_round_end((int*)cur, tr, vi, T, n, S, thr0, traj, vis, (int*)n_active, (hipStream_t)stream);
+}
+
+int sampt_pips2_init_f32(const float* trajs0, const float* fmap, int H, int W, const int32_t* frame_idx, float stride, int S, int n,
+                         int have_init, float* coords, float* bak, float* f1, float* f2, float* f4, sampt_stream_t stream) {
+  if (!trajs0 || !coords || !bak || S <= 0 || n <= 0 || !(stride > 0.f) ||
+      (!have_init && (!fmap || !frame_idx || !f1 || !f2 || !f4 || H <= 0 || W <= 0)))
+    return fail(SAMPT_ERR_ARG, "sampt_pips2_init_f32: bad arguments");
+  return pips2_init(trajs0, fmap, H, W, (const int*)frame_idx, stride, S, n, have_init, coords, bak, f1, f2, f4, (hipStream_t)stream);
+}
+
+int sampt_pips2_templates_f32(const float* fmap, int H, int W, const int32_t* frame_idx, const float* coords, int S, int n, float* f2,
+                              float* f4, sampt_stream_t stream) {
+  if (!fmap || !frame_idx || !coords || !f2 || !f4 || H <= 0 || W <= 0 || S <= 0 || n <= 0)
+    return fail(SAMPT_ERR_ARG, "sampt_pips2_templates_f32: bad arguments");
+  return pips2_templates(fmap, H, W, (const int*)frame_idx, coords, S, n, f2, f4, (hipStream_t)stream);
+}
+
+int sampt_pips2_build_input_f32(const float* coords, const float* omega, int S, int n, float* x, int ldx, sampt_stream_t stream) {
+  if (!coords || !omega || !x || S <= 0 || n <= 0 || ldx != 720)
+    return fail(SAMPT_ERR_ARG, "sampt_pips2_build_input_f32: bad arguments (null pointer, S, n <= 0 or ldx != 720)");
+  return pips2_build_input(coords, omega, S, n, x, ldx, (hipStream_t)stream);
+}
+
+int sampt_instnorm1d_relu_f32(const float* x, float* y, int n, int S, int C, sampt_stream_t stream) {
+  if (!x || !y || n <= 0 || S <= 0 || C <= 0) return fail(SAMPT_ERR_ARG, "sampt_instnorm1d_relu_f32: bad arguments");
+  return instnorm1d_relu(x, y, n, S, C, (hipStream_t)stream);
+}
+
+int sampt_add_chanpad_f32(float* out, const float* identity, long rows, int cin, int cout, int relu, sampt_stream_t stream) {
+  if (!out || !identity || rows <= 0 || cin <= 0 || cout < cin) return fail(SAMPT_ERR_ARG, "sampt_add_chanpad_f32: bad arguments");
+  return add_chanpad(out, identity, rows, cin, cout, relu, (hipStream_t)stream);
+}
+
+int sampt_pips2_apply_delta_f32(const float* delta, const float* bak, float stride, int S, int n, int last, float* coords, float* trajs,
+                                sampt_stream_t stream) {
+  if (!delta || !bak || !coords || (last && !trajs) || S <= 0 || n <= 0)
+    return fail(SAMPT_ERR_ARG, "sampt_pips2_apply_delta_f32: bad arguments");
+  return pips2_apply_delta(delta, bak, stride, S, n, last, coords, trajs, (hipStream_t)stream);
+}
+
+int sampt_cot_prepare(const float* qxy, const int32_t* qt, const int32_t* frame_map, float stride, int n, int T, float* xy0,
+                      int32_t* fidx_pt, float* traj_out, float* vis_out, sampt_stream_t stream) {
+  if (!qxy || !qt || !frame_map || !xy0 || !fidx_pt || !traj_out || !vis_out || n <= 0 || T <= 0 || !(stride > 0.f))
+    return fail(SAMPT_ERR_ARG, "sampt_cot_prepare: bad arguments");
+  return cot_prepare(qxy, (const int*)qt, (const int*)frame_map, stride, n, T, xy0, (int*)fidx_pt, traj_out, vis_out, (hipStream_t)stream);
+}
+
+int sampt_cot_window_init(int ind, int S_local, int prev, int na, int S, const int32_t* qt, const float* xy0, const int32_t* frame_map,
+                          const float* coords_prev, const float* vis_prev, const float* feat_init, float* coords, float* visin,
+                          float* mask, int32_t* fidx, float* ffeats, sampt_stream_t stream) {
+  if (!qt || !xy0 || !frame_map || !feat_init || !coords || !visin || !mask || !fidx || !ffeats || ind < 0 || S <= 0 || S_local <= 0 ||
+      S_local > S || na <= 0 || prev < 0 || prev > na || (prev > 0 && (!coords_prev || !vis_prev)))
+    return fail(SAMPT_ERR_ARG, "sampt_cot_window_init: bad arguments (0 <= prev <= na, 1 <= S_local <= S, carries needed when prev > 0)");
+  return cot_window_init(ind, S_local, prev, na, S, (const int*)qt, xy0, (const int*)frame_map, coords_prev, vis_prev, feat_init, coords,
+                         visin, mask, (int*)fidx, ffeats, (hipStream_t)stream);
+}
+
+int sampt_cot_pos_embed_f32(const float* coords, const float* pos_x, const float* pos_y, int H, int W, int E, int na, float* pos,
+                            sampt_stream_t stream) {
+  if (!coords || !pos_x || !pos_y || !pos || H <= 0 || W <= 0 || E <= 0 || (E & 1) || na <= 0)
+    return fail(SAMPT_ERR_ARG, "sampt_cot_pos_embed_f32: bad arguments");
+  return cot_pos_embed(coords, pos_x, pos_y, H, W, E, na, pos, (hipStream_t)stream);
+}
+
+int sampt_cot_build_input_f32(const float* ffeats, const float* coords, const float* visin, const float* mask, const float* pos,
+                              const float* times, int S, int na, float* x, sampt_stream_t stream) {
+  if (!ffeats || !coords || !visin || !mask || !pos || !times || !x || S <= 0 || na <= 0)
+    return fail(SAMPT_ERR_ARG, "sampt_cot_build_input_f32: bad arguments");
+  return cot_build_input(ffeats, coords, visin, mask, pos, times, S, na, x, (hipStream_t)stream);
+}
+
+int sampt_cot_window_store_f32(const float* ffeats, const float* vis_w, const float* vis_b, const float* coords, float stride, int S,
+                               int na, int ind, int S_local, int n_total, float* coords_prev, float* vis_prev, float* traj_out,
+                               float* vis_out, sampt_stream_t stream) {
+  if (!ffeats || !vis_w || !vis_b || !coords || !coords_prev || !vis_prev || !traj_out || !vis_out || S <= 0 || na <= 0 || ind < 0 ||
+      S_local <= 0 || S_local > S || n_total < na)
+    return fail(SAMPT_ERR_ARG, "sampt_cot_window_store_f32: bad arguments (1 <= S_local <= S, na <= n_total)");
+  return cot_window_store(ffeats, vis_w, vis_b, coords, stride, S, na, ind, S_local, n_total, coords_prev, vis_prev, traj_out, vis_out,
+                          (hipStream_t)stream);
 }
 
 int sampt_pips_mix_mlp_f32(const float* x, const float* lnw, const float* lnb, const float* w1, const float* b1, const float* w2,
