@@ -1,69 +1,18 @@
-// Device helpers of the DAVIS J / F kernels (vos_metrics.hip, vos_pairs.hip): the description of a source of binary images, the
-// loader of a tile of 64 rows x 256 columns into 64-bit column words (4 pixels per load from any pixel address), seg2bmap on those
-// words, and the table of the disk's spans.  Everything is internal to the translation unit that includes it.
+// Device helpers of the DAVIS J / F kernels (vos_metrics.hip, vos_pairs.hip) on top of the bit-plane tile reader (bitplane.h): a
+// tile's column words with the column east of it and the row below it, seg2bmap on those words, the table of the disk's spans and
+// the disk dilation of a tile of boundary words.  Everything is internal to the translation unit that includes it.
 #pragma once
-#include "ops.h"
+#include "bitplane.h"
 
 namespace sampt {
 
 namespace {
-typedef unsigned long long u64;
-typedef unsigned int u32;
-
-// 4 pixels in one load from any pixel address: rows of a width that is no multiple of 4 start at any byte (f32: any 4-byte) offset
-typedef float jf_f32x4 __attribute__((ext_vector_type(4), aligned(4)));
-typedef unsigned int jf_u8x4 __attribute__((aligned(1)));
-
-constexpr int JF_MAX_BLOCKS = 1 << 20;       // grid cap (stride loops beyond)
 constexpr int JF_MAX_R = 64;                 // one band of halo above and below
-constexpr int JF_KIND_BYTES = 0, JF_KIND_F32 = 1, JF_KIND_INDEX = 2;
-
-struct JfSrc {
-  const void* base;                          // stack of planes [.][h][w]
-  const int* planes;                         // plane of item i (null: plane i)
-  const int* values;                         // JF_KIND_INDEX: the value of item i
-  float thr;
-  int kind;
-};
 
 // disk rows per level: the dx whose column span is V_k are lo[k] .. hi[k] (none if lo > hi)
 struct JfDisk {
   unsigned char lo[JF_MAX_R + 1], hi[JF_MAX_R + 1];
 };
-
-template <int KIND>
-__device__ __forceinline__ u32 jf_on(const void* p, long idx, float thr, int val) {
-  if (KIND == JF_KIND_F32) return ((const float*)p)[idx] > thr ? 1u : 0u;
-  if (KIND == JF_KIND_INDEX) return (int)((const unsigned char*)p)[idx] == val ? 1u : 0u;
-  return ((const unsigned char*)p)[idx] != 0 ? 1u : 0u;
-}
-
-// pixels (y, x .. x + 3) of a row starting at element `row` -> acc[c] |= on << j
-template <int KIND, bool VEC>
-__device__ __forceinline__ void jf_row4(const void* p, long row, int x, int w, float thr, int val, int j, u32* acc) {
-  if (VEC) {
-    if (KIND == JF_KIND_F32) {
-      const jf_f32x4 v = *(const jf_f32x4*)((const float*)p + row + x);
-      acc[0] |= (v.x > thr ? 1u : 0u) << j, acc[1] |= (v.y > thr ? 1u : 0u) << j;
-      acc[2] |= (v.z > thr ? 1u : 0u) << j, acc[3] |= (v.w > thr ? 1u : 0u) << j;
-    } else {
-      const u32 v = *(const jf_u8x4*)((const unsigned char*)p + row + x);
-      if (KIND == JF_KIND_INDEX) {
-        acc[0] |= ((int)(v & 0xffu) == val ? 1u : 0u) << j, acc[1] |= ((int)((v >> 8) & 0xffu) == val ? 1u : 0u) << j;
-        acc[2] |= ((int)((v >> 16) & 0xffu) == val ? 1u : 0u) << j, acc[3] |= ((int)(v >> 24) == val ? 1u : 0u) << j;
-      } else {
-        acc[0] |= ((v & 0xffu) ? 1u : 0u) << j, acc[1] |= ((v & 0xff00u) ? 1u : 0u) << j;
-        acc[2] |= ((v & 0xff0000u) ? 1u : 0u) << j, acc[3] |= ((v & 0xff000000u) ? 1u : 0u) << j;
-      }
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int xc = x + c < w ? x + c : w - 1;                // (clamped: the load is always inside the row; unused beyond w)
-      acc[c] |= jf_on<KIND>(p, row + xc, thr, val) << j;
-    }
-  }
-}
 
 // what one lane knows of one image around its 4 columns of a tile
 struct JfBits {
@@ -72,63 +21,35 @@ struct JfBits {
   u32 below;                                 // bit c: pixel (y0 + 64, x0 + c); bit 4: (y0 + 64, column after the tile)
 };
 
-// every load is unconditional on a clamped index and masked afterwards (rows past h re-read row h - 1, lanes past w the row's end)
+// bp_words plus the east column and the row below, loaded by bitplane.h's rules: unconditional on a clamped index, masked afterwards
 template <int KIND, bool VEC>
-__device__ __forceinline__ void jf_bits_k(const void* p, float thr, int val, int y0, int x0, int xe, int h, int w, int lane,
-                                          JfBits& b) {
-  // VEC (w >= 4): a lane whose 4 pixels would pass the row's end loads the row's last 4 and moves its columns down afterwards
-  const int xl = VEC ? (x0 + 4 <= w ? x0 : w - 4) : (x0 < w ? x0 : w - 1);
+__device__ __forceinline__ void jf_bits_k(const void* p, float thr, int val, const BpTile& k, int h, int w, int lane, JfBits& b) {
+  const int y0 = k.y0, x0 = k.x0, xe = k.xe;
   const int ye = y0 + lane < h ? y0 + lane : h - 1, yb = y0 + 64 < h ? y0 + 64 : h - 1;
   const int xec = xe < w ? xe : w - 1;
-  const u32 e_on = jf_on<KIND>(p, (long)ye * w + xec, thr, val);
+  const u32 e_on = bp_on<KIND>(p, (long)ye * w + xec, thr, val);
   u32 below = 0;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     const int xc = x0 + c < w ? x0 + c : w - 1;
-    below |= jf_on<KIND>(p, (long)yb * w + xc, thr, val) << c;
+    below |= bp_on<KIND>(p, (long)yb * w + xc, thr, val) << c;
   }
-  below |= jf_on<KIND>(p, (long)yb * w + xec, thr, val) << 4;
-  u64 word[4] = {0, 0, 0, 0};
-#pragma unroll 1
-  for (int g = 0; g < 4; ++g) {                                // a real loop, as in k_rle_words: 16 rows' loads in flight, then their bits
-    u32 piece[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int y = y0 + g * 16 + j < h ? y0 + g * 16 + j : h - 1;
-      jf_row4<KIND, VEC>(p, (long)y * w, xl, w, thr, val, j, piece);
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) word[c] |= (u64)piece[c] << (g * 16);
-  }
-  if (VEC) {
-    const int d = x0 < w ? x0 - xl : 0;                        // 0 .. 3: column x0 + c was loaded as column c + d (beyond w: masked below)
-    const u64 w0 = word[0], w1 = word[1], w2 = word[2], w3 = word[3];
-    word[0] = d == 0 ? w0 : d == 1 ? w1 : d == 2 ? w2 : w3;
-    word[1] = d == 0 ? w1 : d == 1 ? w2 : w3;
-    word[2] = d == 0 ? w2 : w3;
-  }
+  below |= bp_on<KIND>(p, (long)yb * w + xec, thr, val) << 4;
+  bp_words<KIND, VEC>(p, thr, val, y0, x0, h, w, b.word);
   const int rows = h - y0 < 64 ? h - y0 : 64;
   const u64 vmask = rows == 64 ? ~0ull : (1ull << rows) - 1ull;
-  u32 bmask = 0;
+  u32 bmask = xe < w ? 1u << 4 : 0u;
 #pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const bool in = x0 + c < w;
-    b.word[c] = in ? word[c] & vmask : 0ull;
-    bmask |= (in ? 1u : 0u) << c;
-  }
-  bmask |= (xe < w ? 1u : 0u) << 4;
+  for (int c = 0; c < 4; ++c) bmask |= (x0 + c < w ? 1u : 0u) << c;
   b.east = xe < w ? (u64)__ballot(e_on != 0) & vmask : 0ull;
   b.below = y0 + 64 < h ? below & bmask : 0u;
 }
 
 template <int KIND, bool VEC>
-__device__ __forceinline__ void jf_bits(const JfSrc& s, long item, long npix, int y0, int x0, int xe, int h, int w, int lane,
-                                        JfBits& b) {
-  const long plane = s.planes ? (long)s.planes[item] : item;
-  const int val = KIND == JF_KIND_INDEX ? s.values[item] : 0;
-  const void* p = KIND == JF_KIND_F32 ? (const void*)((const float*)s.base + plane * npix)
-                                      : (const void*)((const unsigned char*)s.base + plane * npix);
-  jf_bits_k<KIND, VEC>(p, s.thr, val, y0, x0, xe, h, w, lane, b);
+__device__ __forceinline__ void jf_bits(const BpSrc& s, long item, long npix, const BpTile& k, int h, int w, int lane, JfBits& b) {
+  int val;
+  const void* p = bp_plane<KIND>(s, item, npix, val);
+  jf_bits_k<KIND, VEC>(p, s.thr, val, k, h, w, lane, b);
 }
 
 __device__ __forceinline__ void jf_clear(JfBits& b, const JfBits& v) {
@@ -161,10 +82,45 @@ __device__ __forceinline__ void jf_boundary(const JfBits& b, int y0, int x0, int
   }
 }
 
-__device__ __forceinline__ int jf_wave_sum(int v) {
+// The disk dilation of a tile of 64 rows x 256 columns of a plane of words src [nb][w], one thread per column.  jf_halo: the
+// thread's two columns tid and tid + 256 of the 256 + 2 r halo columns, in the tile's band (mid) and the bands above and below.
+__device__ __forceinline__ void jf_halo(const u64* __restrict__ src, const BpTile& k, int nb, int w, int r, int tid, u64* mid, u64* up,
+                                        u64* dn) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;                                                    // (lane 0 holds the sum)
+  for (int i = 0; i < 2; ++i) {                                // halo column tid + 256 i of 256 + 2 r = image column xx
+    const int hc = tid + i * 256, xx = k.cb * 256 - r + hc;
+    const bool ok = hc < 256 + 2 * r && xx >= 0 && xx < w;
+    mid[i] = ok ? src[(long)k.rb * w + xx] : 0ull;
+    up[i] = ok && k.rb > 0 ? src[(long)(k.rb - 1) * w + xx] : 0ull;
+    dn[i] = ok && k.rb + 1 < nb ? src[(long)(k.rb + 1) * w + xx] : 0ull;
+  }
+}
+
+// jf_dilate: the vertical dilations V_k (k = 0 .. r) of the halo columns grow in registers; the disk is the union over dx of
+// V_isqrt(r^2 - dx^2)(x + dx): a level that some dx uses is staged in lv (two buffers in turn, one barrier per level) and every
+// thread ORs the columns x +- dx of it.  Returns the dilation of the thread's column (bits of rows >= h not cleared).
+// The caller has passed a workgroup barrier since lv's previous readers: the first level is written without one.  Inside, a
+// level's buffer is rewritten only two levels later, past the barrier its readers have passed.
+__device__ __forceinline__ u64 jf_dilate(const u64* mid, const u64* up, const u64* dn, int r, const JfDisk& disk,
+                                         u64 (*lv)[256 + 2 * JF_MAX_R], int tid) {
+  u64 V[2] = {mid[0], mid[1]};
+  u64 D = 0;
+  int p = 0;
+  for (int k = 0; k <= r; ++k) {
+    if (k > 0) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)                              // rows y - k and y + k (k = 64: the neighbouring bands themselves)
+        V[i] |= k < 64 ? (mid[i] << k) | (up[i] >> (64 - k)) | (mid[i] >> k) | (dn[i] << (64 - k)) : up[i] | dn[i];
+    }
+    const int lo = disk.lo[k], hi = disk.hi[k];
+    if (lo > hi) continue;                                     // no dx has this half-height
+    lv[p][tid] = V[0];
+    if (tid + 256 < 256 + 2 * r) lv[p][tid + 256] = V[1];
+    __syncthreads();                                           // (the buffer written two levels on is free: its readers passed here)
+    for (int dx = lo; dx <= hi; ++dx) D |= lv[p][tid + r - dx] | lv[p][tid + r + dx];
+    p ^= 1;
+  }
+  return D;
 }
 
 // ---- host side
@@ -183,13 +139,6 @@ inline JfDisk jf_disk(int r) {
     disk.hi[k] = (unsigned char)jf_isqrt(r * r - k * k);
   }
   return disk;
-}
-
-inline bool jf_src(JfSrc& s, const void* base, int kind, float thr, const int* values, const int* planes, int w) {
-  if (kind != JF_KIND_BYTES && kind != JF_KIND_F32 && kind != JF_KIND_INDEX) return false;
-  if (!base || (kind == JF_KIND_INDEX && !values) || (kind == JF_KIND_F32 && ((uintptr_t)base & 3))) return false;
-  s.base = base, s.planes = planes, s.values = kind == JF_KIND_INDEX ? values : nullptr, s.thr = thr, s.kind = kind;
-  return true;
 }
 }  // namespace
 

@@ -3,13 +3,13 @@
 // x == thr are clear).  Runs go over the column-major flattening p = x * h + y, the first run counts zeros.
 //
 // Only the pass over the pixels is hot:
-//   k_rle_words   one wave per block of 64 rows x 256 columns.  Per row every lane loads 4 adjacent pixels (one 4-byte or one
-//                 16-byte load: the wave reads a contiguous 256 B / 1 KiB segment) and shifts them into four 64-bit column
-//                 words held in registers (bit j = row y0 + j); no LDS.  transitions = word ^ ((word << 1) | carry), carry =
+//   k_rle_words   one wave per tile of 64 rows x 256 columns, read by the tile reader of csrc/bitplane.h: per row every lane loads 4
+//                 adjacent pixels (one 4-byte or one 16-byte load: the wave reads a contiguous 256 B / 1 KiB segment) into four
+//                 64-bit column words held in registers (bit j = row y0 + j); no LDS.  transitions = word ^ ((word << 1) | carry), carry =
 //                 the pixel before the word in column-major order: (y0 - 1, x), or (h - 1, x - 1) for the first word of a
 //                 column, or 0 for the first pixel of a mask (so a mask that starts set opens with a 0 run and nothing leaks
 //                 from the mask before it).  Written per word: the transition word, popcount(transitions) | popcount(word) << 16.
-//                 Rows that are not 4-byte (f32: 16-byte) aligned take the element-load form of the same kernel.
+//                 Any width and base take the 4-pixel loads; only images narrower than 4 take the element-load form.
 // The rest moves a thousandth of that:
 //   k_rle_scan    one workgroup per mask walks its words in run order (x, then row block): exclusive sum of the transition
 //                 counts, exclusive max of the last transition's position, the mask's area and number of runs
@@ -21,14 +21,11 @@
 // Workspace (storage order [mask][row block][x], so the hot kernel's stores are contiguous per wave): 8 B transition word +
 // 4 B count (then: run offset inside the mask) + 4 B previous position per 64 pixels of a column, + 16 B per mask.
 #include "ops.h"
+#include "bitplane.h"
 
 namespace sampt {
 
 namespace {
-typedef unsigned long long u64;
-typedef unsigned int u32;
-
-constexpr int RLE_MAX_BLOCKS = 1 << 20;      // grid cap of the per-tile / per-word kernels (stride loops beyond)
 constexpr int STR_PER_THREAD = 8, STR_PER_BLOCK = 256 * STR_PER_THREAD;
 
 struct OpAdd {
@@ -66,51 +63,20 @@ __device__ __forceinline__ V block_scan_excl(V v, Op op, V zero, V* sm, V& total
   }
   return op(pre, exc);
 }
-
-template <bool F32>
-__device__ __forceinline__ u32 rle_on(const void* base, long idx, float thr) {
-  if (F32) return ((const float*)base)[idx] > thr ? 1u : 0u;
-  return ((const unsigned char*)base)[idx] != 0 ? 1u : 0u;
-}
-
-// pixels (y, x .. x + 3) of a row starting at element `row` -> acc[c] |= on << j
-template <bool F32, bool VEC>
-__device__ __forceinline__ void rle_row4(const void* base, long row, int x, int w, float thr, int j, u32* acc) {
-  if (VEC) {
-    if (F32) {
-      const float4 v = *(const float4*)((const float*)base + row + x);
-      acc[0] |= (v.x > thr ? 1u : 0u) << j, acc[1] |= (v.y > thr ? 1u : 0u) << j;
-      acc[2] |= (v.z > thr ? 1u : 0u) << j, acc[3] |= (v.w > thr ? 1u : 0u) << j;
-    } else {
-      const u32 v = *(const u32*)((const unsigned char*)base + row + x);
-      acc[0] |= ((v & 0xffu) ? 1u : 0u) << j, acc[1] |= ((v & 0xff00u) ? 1u : 0u) << j;
-      acc[2] |= ((v & 0xff0000u) ? 1u : 0u) << j, acc[3] |= ((v & 0xff000000u) ? 1u : 0u) << j;
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int xc = x + c < w ? x + c : w - 1;                // (clamped: the load is always inside the row; unused beyond w)
-      acc[c] |= rle_on<F32>(base, row + xc, thr) << j;
-    }
-  }
-}
 }  // namespace
 
-// tiles = n * nb * ncb in (mask, row block, column block) order; VEC: w % 4 == 0 and the base is 4-byte (F32: 16-byte) aligned
-template <bool F32, bool VEC>
+// tiles = n * nb * ncb in (mask, row block, column block) order; KIND: bytes or f32; VEC: 4 pixels per load (w >= 4); WVEC: w % 4 == 0
+// (a template argument here, not the run-time flag of the other pixel kernels: with the column move-down and both store forms
+// compiled in, the bytes / VEC kernel spills SGPRs into a 73rd VGPR and loses its 7th wave per SIMD on the aligned widths)
+template <int KIND, bool VEC, bool WVEC>
 __global__ __launch_bounds__(256) void k_rle_words(const void* __restrict__ x_in, float thr, int h, int w, int nb, int ncb, long tiles,
                                                    u64* __restrict__ tw, u32* __restrict__ cp) {
   const int lane = threadIdx.x & 63;
   const long npix = (long)h * w;
   for (long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6); t < tiles; t += (long)gridDim.x * 4) {   // wave-uniform
-    const int cb = (int)(t % ncb);
-    const long r = t / ncb;
-    const int rb = (int)(r % nb);
-    const long m = r / nb;
-    const int y0 = rb * 64, x0 = cb * 256 + lane * 4;
-    const void* base = F32 ? (const void*)((const float*)x_in + m * npix) : (const void*)((const unsigned char*)x_in + m * npix);
-    // every load below is unconditional: rows past h re-read row h - 1, lanes past w re-read the row's last pixels
-    const int xl = x0 < w ? x0 : (VEC ? w - 4 : w - 1);
+    const BpTile k = bp_tile(t, nb, ncb, lane);
+    const int y0 = k.y0, x0 = k.x0;
+    const void* base = bp_plane<KIND>(x_in, k.item, npix);
     // carries first (their latency hides under the rows): unconditional loads of a clamped index, masked afterwards
     u32 carry[4];
 #pragma unroll
@@ -118,42 +84,22 @@ __global__ __launch_bounds__(256) void k_rle_words(const void* __restrict__ x_in
       const int xc = x0 + c;
       const bool has = xc < w && (y0 > 0 || xc > 0);           // (the first pixel of a mask has no predecessor)
       const long ci = !has ? 0 : (y0 > 0 ? (long)(y0 - 1) * w + xc : (long)(h - 1) * w + xc - 1);
-      carry[c] = rle_on<F32>(base, ci, thr) & (has ? 1u : 0u);
+      carry[c] = bp_on<KIND>(base, ci, thr, 0) & (has ? 1u : 0u);
     }
-    u64 word[4] = {0, 0, 0, 0};
-#pragma unroll 1
-    for (int g = 0; g < 4; ++g) {                              // a real loop: 16 rows' loads in flight per wave, then their bits
-      u32 piece[4] = {0, 0, 0, 0};                             // (fully unrolled, all 64 loads are hoisted: 256 VGPRs, one wave per SIMD)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const int y = y0 + g * 16 + j < h ? y0 + g * 16 + j : h - 1;
-        rle_row4<F32, VEC>(base, (long)y * w, xl, w, thr, j, piece);
-      }
-#pragma unroll
-      for (int c = 0; c < 4; ++c) word[c] |= (u64)piece[c] << (g * 16);
-    }
+    u64 word[4];
+    bp_words<KIND, VEC, VEC && !WVEC>(base, thr, 0, y0, x0, h, w, word);
     const int rows = h - y0 < 64 ? h - y0 : 64;
-    const u64 vmask = rows == 64 ? ~0ull : (1ull << rows) - 1ull;
+    const u64 vmask = rows == 64 ? ~0ull : (1ull << rows) - 1ull;   // (the words are masked already; the bit shifted in is not)
     u64 tr[4];
     u32 cnt[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const u64 wd = word[c] & vmask;
-      tr[c] = (wd ^ ((wd << 1) | carry[c])) & vmask;
-      cnt[c] = (u32)__popcll(tr[c]) | ((u32)__popcll(wd) << 16);
+      tr[c] = (word[c] ^ ((word[c] << 1) | carry[c])) & vmask;
+      cnt[c] = (u32)__popcll(tr[c]) | ((u32)__popcll(word[c]) << 16);
     }
-    const long s = (m * nb + rb) * (long)w + x0;
-    if (VEC) {
-      if (x0 < w) {                                            // s % 4 == 0: 32-byte / 16-byte aligned
-        *(ulonglong2*)(tw + s) = make_ulonglong2(tr[0], tr[1]);
-        *(ulonglong2*)(tw + s + 2) = make_ulonglong2(tr[2], tr[3]);
-        *(uint4*)(cp + s) = make_uint4(cnt[0], cnt[1], cnt[2], cnt[3]);
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (x0 + c < w) tw[s + c] = tr[c], cp[s + c] = cnt[c];
-    }
+    const long s = (k.item * nb + k.rb) * (long)w + x0;
+    bp_store4(tw + s, tr, x0, w, WVEC);
+    bp_store4(cp + s, cnt, x0, w, WVEC);
   }
 }
 
@@ -322,11 +268,10 @@ __global__ __launch_bounds__(256) void k_str_blocks(long long* __restrict__ bsum
 }
 
 // --------------------------------------------------------------------------------------------------------------------
-static bool rle_shape_ok(int n, int h, int w) { return n >= 0 && h > 0 && w > 0 && (long)h * w < (1L << 31); }
 static size_t rle_bytes_per_mask(int h, int w) { return (size_t)w * cdiv(h, 64) * 16 + 16; }
 
 size_t rle_workspace_bytes(int n, int h, int w) {
-  if (n <= 0 || !rle_shape_ok(n, h, w)) return 0;
+  if (n <= 0 || !bp_shape_ok(n, h, w)) return 0;
   return (size_t)n * rle_bytes_per_mask(h, w);
 }
 
@@ -348,7 +293,7 @@ RleWs rle_carve(void* ws, int n, int h, int w) {
 
 int rle_count(const void* x, int is_f32, float thr, int n, int h, int w, long long* offsets, int* area, void* ws, size_t ws_bytes,
               hipStream_t s) {
-  if (!rle_shape_ok(n, h, w)) return SAMPT_ERR_ARG;
+  if (!bp_shape_ok(n, h, w)) return SAMPT_ERR_ARG;
   if (!offsets) return SAMPT_ERR_ARG;
   if (n > 0 && (!x || !area || !ws || ((uintptr_t)ws & 15) || (is_f32 && ((uintptr_t)x & 3)))) return SAMPT_ERR_ARG;
   if (n > 0 && ws_bytes < rle_workspace_bytes(n, h, w)) return SAMPT_ERR_WORKSPACE;
@@ -356,15 +301,12 @@ int rle_count(const void* x, int is_f32, float thr, int n, int h, int w, long lo
     const RleWs k = rle_carve(ws, n, h, w);
     const int nb = cdiv(h, 64), ncb = cdiv(w, 256);
     const long tiles = (long)n * nb * ncb;
-    const int blocks = (int)((tiles + 3) / 4 < RLE_MAX_BLOCKS ? (tiles + 3) / 4 : RLE_MAX_BLOCKS);
-    const bool vec = w % 4 == 0 && ((uintptr_t)x & (is_f32 ? 15 : 3)) == 0;
-    if (is_f32) {
-      if (vec) hipLaunchKernelGGL((k_rle_words<true, true>), dim3(blocks), dim3(256), 0, s, x, thr, h, w, nb, ncb, tiles, k.tw, k.cp);
-      else hipLaunchKernelGGL((k_rle_words<true, false>), dim3(blocks), dim3(256), 0, s, x, thr, h, w, nb, ncb, tiles, k.tw, k.cp);
-    } else {
-      if (vec) hipLaunchKernelGGL((k_rle_words<false, true>), dim3(blocks), dim3(256), 0, s, x, thr, h, w, nb, ncb, tiles, k.tw, k.cp);
-      else hipLaunchKernelGGL((k_rle_words<false, false>), dim3(blocks), dim3(256), 0, s, x, thr, h, w, nb, ncb, tiles, k.tw, k.cp);
-    }
+    typedef void (*words_fn)(const void*, float, int, int, int, int, long, u64*, u32*);
+#define RLE_W(kind) {k_rle_words<kind, false, false>, k_rle_words<kind, true, false>, k_rle_words<kind, true, true>}
+    static const words_fn table[2][3] = {RLE_W(BP_KIND_BYTES), RLE_W(BP_KIND_F32)};   // w < 4; w % 4 != 0; w % 4 == 0
+#undef RLE_W
+    hipLaunchKernelGGL(table[is_f32 ? 1 : 0][w < 4 ? 0 : w % 4 ? 1 : 2], dim3(bp_blocks(tiles, 4)), dim3(256), 0, s, x, thr, h, w, nb, ncb,
+                       tiles, k.tw, k.cp);
     SAMPT_CHECK_LAUNCH("rle_count words");
     hipLaunchKernelGGL(k_rle_scan, dim3(n < 65535 ? n : 65535), dim3(256), 0, s, (const u64*)k.tw, k.cp, k.pp, n, h, w, nb, k.runs, area);
     SAMPT_CHECK_LAUNCH("rle_count scan");
@@ -375,7 +317,7 @@ int rle_count(const void* x, int is_f32, float thr, int n, int h, int w, long lo
 }
 
 int rle_emit(int n, int h, int w, const long long* offsets, unsigned* counts, const void* ws, size_t ws_bytes, hipStream_t s) {
-  if (!rle_shape_ok(n, h, w)) return SAMPT_ERR_ARG;
+  if (!bp_shape_ok(n, h, w)) return SAMPT_ERR_ARG;
   if (n == 0) return SAMPT_OK;
   if (!offsets || !counts || !ws || ((uintptr_t)ws & 15)) return SAMPT_ERR_ARG;
   if (ws_bytes < rle_workspace_bytes(n, h, w)) return SAMPT_ERR_WORKSPACE;
@@ -394,14 +336,12 @@ size_t rle_string_workspace_bytes(long total) {
   return (size_t)((total + STR_PER_BLOCK - 1) / STR_PER_BLOCK) * 8;
 }
 
-static int str_grid(long nblk) { return (int)(nblk < RLE_MAX_BLOCKS ? nblk : RLE_MAX_BLOCKS); }
-
 int rle_string_sizes(const unsigned* counts, const long long* offsets, int n, long total, long long* str_offsets, void* ws,
                      size_t ws_bytes, hipStream_t s) {
   if (n <= 0 || total < n || !counts || !offsets || !str_offsets || !ws || ((uintptr_t)ws & 7)) return SAMPT_ERR_ARG;
   if (ws_bytes < rle_string_workspace_bytes(total)) return SAMPT_ERR_WORKSPACE;
   const long nblk = (total + STR_PER_BLOCK - 1) / STR_PER_BLOCK;
-  hipLaunchKernelGGL(k_str<0>, dim3(str_grid(nblk)), dim3(256), 0, s, counts, offsets, n, total, (long long*)ws, str_offsets,
+  hipLaunchKernelGGL(k_str<0>, dim3(bp_blocks(nblk, 1)), dim3(256), 0, s, counts, offsets, n, total, (long long*)ws, str_offsets,
                      (unsigned char*)nullptr);
   SAMPT_CHECK_LAUNCH("rle_string_sizes lengths");
   hipLaunchKernelGGL(k_str_blocks, dim3(1), dim3(256), 0, s, (long long*)ws, nblk, n, str_offsets);
@@ -414,7 +354,7 @@ int rle_string_emit(const unsigned* counts, const long long* offsets, int n, lon
   if (n <= 0 || total < n || !counts || !offsets || !str_offsets || !chars || !ws || ((uintptr_t)ws & 7)) return SAMPT_ERR_ARG;
   if (ws_bytes < rle_string_workspace_bytes(total)) return SAMPT_ERR_WORKSPACE;
   const long nblk = (total + STR_PER_BLOCK - 1) / STR_PER_BLOCK;
-  hipLaunchKernelGGL(k_str<1>, dim3(str_grid(nblk)), dim3(256), 0, s, counts, offsets, n, total, (long long*)const_cast<void*>(ws),
+  hipLaunchKernelGGL(k_str<1>, dim3(bp_blocks(nblk, 1)), dim3(256), 0, s, counts, offsets, n, total, (long long*)const_cast<void*>(ws),
                      str_offsets, chars);
   SAMPT_CHECK_LAUNCH("rle_string_emit");
   return SAMPT_OK;

@@ -3,13 +3,12 @@
 // division per IoU (this file is built without fp contraction, see the Makefile): every result is bitwise repeatable and equals the
 // host restatement of sam_pt_amd/vis_metrics.py exactly.
 //
-// Bit-plane format (public, include/sampt_hip.h; the layout k_jf_words of csrc/vos_metrics.hip writes for its boundary planes): a stack
+// Bit-plane format (public, include/sampt_hip.h; the column words of csrc/bitplane.h, stored): a stack
 // [n][h][w] becomes uint64 [n][ceil(h / 64)][w]; bit j of word (band b, column x) is pixel (64 b + j, x); bits of rows >= h are 0.
 //
-//   k_bits_pack     one wave per tile of 64 rows x 256 columns, the tile shape and the loaders of k_rle_words / k_jf_words (restated
-//                   here: those kernels stay what they are): per row every lane loads 4 adjacent pixels with one 4-byte or 16-byte
-//                   load from any pixel address, a lane at a row's end loads the row's last 4 pixels and moves its columns down,
-//                   images narrower than 4 take the element-load form.  Every pixel is read once; the area is an integer atomic.
+//   k_bits_pack     one wave per tile of 64 rows x 256 columns: the tile reader of csrc/bitplane.h (4 pixels per load from any pixel
+//                   address; images narrower than 4 take the element-load form), its words stored as they are.  Every pixel is read
+//                   once; the area is an integer atomic.
 //   k_rle_scan      one workgroup per mask: inclusive prefix sums (uint64) of the mask's runs into the workspace, the sum of the odd
 //                   runs (the area) and the status (the runs must sum to h * w).
 //   k_rle_bits      one thread per output word: a binary search for the run that holds position x * h + 64 b, then a walk over the
@@ -23,127 +22,34 @@
 //   k_seq_iou_sum   one thread per pair: adds the partials in a fixed order, union = sum of the present frames' areas - inter.
 //   k_vis_match     one wave per area range, one lane per IoU threshold; the per-threshold "matched" flags live in LDS.
 #include "ops.h"
+#include "bitplane.h"
 
 namespace sampt {
 
 namespace {
-typedef unsigned long long u64;
-typedef unsigned int u32;
-
-// 4 pixels in one load from any pixel address: rows of a width that is no multiple of 4 start at any byte (f32: any 4-byte) offset
-typedef float ve_f32x4 __attribute__((ext_vector_type(4), aligned(4)));
-typedef unsigned int ve_u8x4 __attribute__((aligned(1)));
-
-constexpr int VE_MAX_BLOCKS = 1 << 20;       // grid cap (stride loops beyond)
-constexpr int VE_KIND_BYTES = 0, VE_KIND_F32 = 1, VE_KIND_INDEX = 2;
 constexpr int SI_B = 32;                     // detections / ground truths per tile
 constexpr int SI_KW = 64;                    // word positions per step
 constexpr int SI_TARGET_BLOCKS = 1024;       // workgroups of one call (about 4 per CU)
 constexpr int VM_MAX_G = 960;                // 66 bytes of LDS per ground truth
 constexpr int VM_MAX_THR = 64;
-
-template <int KIND>
-__device__ __forceinline__ u32 ve_on(const void* p, long idx, float thr, int val) {
-  if (KIND == VE_KIND_F32) return ((const float*)p)[idx] > thr ? 1u : 0u;
-  if (KIND == VE_KIND_INDEX) return (int)((const unsigned char*)p)[idx] == val ? 1u : 0u;
-  return ((const unsigned char*)p)[idx] != 0 ? 1u : 0u;
-}
-
-// pixels (y, x .. x + 3) of a row starting at element `row` -> acc[c] |= on << j
-template <int KIND, bool VEC>
-__device__ __forceinline__ void ve_row4(const void* p, long row, int x, int w, float thr, int val, int j, u32* acc) {
-  if (VEC) {
-    if (KIND == VE_KIND_F32) {
-      const ve_f32x4 v = *(const ve_f32x4*)((const float*)p + row + x);
-      acc[0] |= (v.x > thr ? 1u : 0u) << j, acc[1] |= (v.y > thr ? 1u : 0u) << j;
-      acc[2] |= (v.z > thr ? 1u : 0u) << j, acc[3] |= (v.w > thr ? 1u : 0u) << j;
-    } else {
-      const u32 v = *(const ve_u8x4*)((const unsigned char*)p + row + x);
-      if (KIND == VE_KIND_INDEX) {
-        acc[0] |= ((int)(v & 0xffu) == val ? 1u : 0u) << j, acc[1] |= ((int)((v >> 8) & 0xffu) == val ? 1u : 0u) << j;
-        acc[2] |= ((int)((v >> 16) & 0xffu) == val ? 1u : 0u) << j, acc[3] |= ((int)(v >> 24) == val ? 1u : 0u) << j;
-      } else {
-        acc[0] |= ((v & 0xffu) ? 1u : 0u) << j, acc[1] |= ((v & 0xff00u) ? 1u : 0u) << j;
-        acc[2] |= ((v & 0xff0000u) ? 1u : 0u) << j, acc[3] |= ((v & 0xff000000u) ? 1u : 0u) << j;
-      }
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int xc = x + c < w ? x + c : w - 1;                // (clamped: the load is always inside the row; unused beyond w)
-      acc[c] |= ve_on<KIND>(p, row + xc, thr, val) << j;
-    }
-  }
-}
-
-// rows y0 .. y0 + 63 of columns x0 .. x0 + 3 of one plane as column words (0 outside the image).  Every load is unconditional on a
-// clamped index and masked afterwards (rows past h re-read row h - 1, lanes past w the row's end).
-template <int KIND, bool VEC>
-__device__ __forceinline__ void ve_words(const void* p, float thr, int val, int y0, int x0, int h, int w, u64* out) {
-  // VEC (w >= 4): a lane whose 4 pixels would pass the row's end loads the row's last 4 and moves its columns down afterwards
-  const int xl = VEC ? (x0 + 4 <= w ? x0 : w - 4) : (x0 < w ? x0 : w - 1);
-  u64 word[4] = {0, 0, 0, 0};
-#pragma unroll 1
-  for (int g = 0; g < 4; ++g) {                                // a real loop, as in k_rle_words: 16 rows' loads in flight, then their bits
-    u32 piece[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int y = y0 + g * 16 + j < h ? y0 + g * 16 + j : h - 1;
-      ve_row4<KIND, VEC>(p, (long)y * w, xl, w, thr, val, j, piece);
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) word[c] |= (u64)piece[c] << (g * 16);
-  }
-  if (VEC) {
-    const int d = x0 < w ? x0 - xl : 0;                        // 0 .. 3: column x0 + c was loaded as column c + d (beyond w: masked below)
-    const u64 w0 = word[0], w1 = word[1], w2 = word[2], w3 = word[3];
-    word[0] = d == 0 ? w0 : d == 1 ? w1 : d == 2 ? w2 : w3;
-    word[1] = d == 0 ? w1 : d == 1 ? w2 : w3;
-    word[2] = d == 0 ? w2 : w3;
-  }
-  const int rows = h - y0 < 64 ? h - y0 : 64;
-  const u64 vmask = rows == 64 ? ~0ull : (1ull << rows) - 1ull;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) out[c] = x0 + c < w ? word[c] & vmask : 0ull;
-}
-
-__device__ __forceinline__ int ve_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;                                                    // (lane 0 holds the sum)
-}
 }  // namespace
 
 // tiles = n * nb * ncb in (item, band, column block) order; out: words [n][nb][w]; area int32 [n] (zeroed)
 template <int KIND, bool VEC>
-__global__ __launch_bounds__(256) void k_bits_pack(const void* __restrict__ base, const int* __restrict__ planes,
-                                                   const int* __restrict__ values, float thr, int h, int w, int nb, int ncb, long tiles,
-                                                   int wvec, u64* __restrict__ out, int* __restrict__ area) {
+__global__ __launch_bounds__(256) void k_bits_pack(BpSrc src, int h, int w, int nb, int ncb, long tiles, int wvec, u64* __restrict__ out,
+                                                   int* __restrict__ area) {
   const int lane = threadIdx.x & 63;
   const long npix = (long)h * w;
   for (long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6); t < tiles; t += (long)gridDim.x * 4) {   // wave-uniform
-    const int cb = (int)(t % ncb);
-    const long q = t / ncb;
-    const int rb = (int)(q % nb);
-    const long item = q / nb;
-    const int y0 = rb * 64, x0 = cb * 256 + lane * 4;
-    const long plane = planes ? (long)planes[item] : item;
-    const int val = KIND == VE_KIND_INDEX ? values[item] : 0;
-    const void* p = KIND == VE_KIND_F32 ? (const void*)((const float*)base + plane * npix)
-                                        : (const void*)((const unsigned char*)base + plane * npix);
+    const BpTile k = bp_tile(t, nb, ncb, lane);
+    int val;
+    const void* p = bp_plane<KIND>(src, k.item, npix, val);
     u64 word[4];
-    ve_words<KIND, VEC>(p, thr, val, y0, x0, h, w, word);
-    u64* po = out + (item * nb + rb) * (long)w + x0;
-    if (wvec) {                                                // w % 4 == 0: 32-byte aligned, x0 < w means all four columns
-      if (x0 < w) *(ulonglong2*)po = make_ulonglong2(word[0], word[1]), *(ulonglong2*)(po + 2) = make_ulonglong2(word[2], word[3]);
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (x0 + c < w) po[c] = word[c];
-    }
+    bp_words<KIND, VEC>(p, src.thr, val, k.y0, k.x0, h, w, word);
+    bp_store4(out + (k.item * nb + k.rb) * (long)w + k.x0, word, k.x0, w, wvec);
     int a = __popcll(word[0]) + __popcll(word[1]) + __popcll(word[2]) + __popcll(word[3]);
-    a = ve_wave_sum(a);
-    if (lane == 0 && a) atomicAdd(area + item, a);
+    a = bp_wave_sum(a);
+    if (lane == 0 && a) atomicAdd(area + k.item, a);
   }
 }
 
@@ -341,20 +247,13 @@ __global__ __launch_bounds__(64) void k_vis_match(const long long* __restrict__ 
 }
 
 // --------------------------------------------------------------------------------------------------------------------
-static bool ve_shape_ok(int n, int h, int w) { return n >= 0 && h > 0 && w > 0 && (long)h * w < (1L << 31); }
-
-static int ve_blocks(long work, long per_block) {
-  const long b = (work + per_block - 1) / per_block;
-  return (int)(b < 1 ? 1 : b < VE_MAX_BLOCKS ? b : VE_MAX_BLOCKS);
-}
-
 int bits_pack(const void* x, int kind, float thr, const int* values, const int* planes, int n, int h, int w, unsigned long long* bits,
               int* area, hipStream_t s) {
-  if (!ve_shape_ok(n, h, w)) return SAMPT_ERR_ARG;
-  if (kind != VE_KIND_BYTES && kind != VE_KIND_F32 && kind != VE_KIND_INDEX) return SAMPT_ERR_ARG;
+  if (!bp_shape_ok(n, h, w) || !bp_kind_ok(kind)) return SAMPT_ERR_ARG;
   if (n == 0) return SAMPT_OK;
-  if (!x || !bits || !area || (kind == VE_KIND_INDEX && !values) || (kind == VE_KIND_F32 && ((uintptr_t)x & 3))) return SAMPT_ERR_ARG;
-  if (((uintptr_t)bits & 15) || ((uintptr_t)area & 3)) return SAMPT_ERR_ARG;
+  BpSrc X;
+  if (!bp_source(X, x, kind, thr, values, planes)) return SAMPT_ERR_ARG;
+  if (!bits || !area || ((uintptr_t)bits & 15) || ((uintptr_t)area & 3)) return SAMPT_ERR_ARG;
   const hipError_t me = hipMemsetAsync(area, 0, (size_t)n * sizeof(int), s);
   if (me != hipSuccess) {
     set_error("bits_pack memset", me);
@@ -362,12 +261,12 @@ int bits_pack(const void* x, int kind, float thr, const int* values, const int* 
   }
   const int nb = cdiv(h, 64), ncb = cdiv(w, 256);
   const long tiles = (long)n * nb * ncb;
-  typedef void (*pack_fn)(const void*, const int*, const int*, float, int, int, int, int, long, int, u64*, int*);
+  typedef void (*pack_fn)(BpSrc, int, int, int, int, long, int, u64*, int*);
   static const pack_fn table[3][2] = {{k_bits_pack<0, false>, k_bits_pack<0, true>},
                                       {k_bits_pack<1, false>, k_bits_pack<1, true>},
                                       {k_bits_pack<2, false>, k_bits_pack<2, true>}};
-  hipLaunchKernelGGL(table[kind][w >= 4 ? 1 : 0], dim3(ve_blocks(tiles, 4)), dim3(256), 0, s, x, planes, kind == VE_KIND_INDEX ? values : nullptr,
-                     thr, h, w, nb, ncb, tiles, w % 4 == 0 ? 1 : 0, (u64*)bits, area);
+  hipLaunchKernelGGL(table[kind][w >= 4 ? 1 : 0], dim3(bp_blocks(tiles, 4)), dim3(256), 0, s, X, h, w, nb, ncb, tiles, w % 4 == 0 ? 1 : 0,
+                     (u64*)bits, area);
   SAMPT_CHECK_LAUNCH("bits_pack");
   return SAMPT_OK;
 }
@@ -376,7 +275,7 @@ size_t rle_decode_workspace_bytes(long total) { return total < 0 ? 0 : (size_t)t
 
 int rle_decode_bits(const unsigned* counts, const long long* offsets, int n, long total, int h, int w, unsigned long long* bits, int* area,
                     int* status, void* ws, size_t ws_bytes, hipStream_t s) {
-  if (!ve_shape_ok(n, h, w) || total < 0) return SAMPT_ERR_ARG;
+  if (!bp_shape_ok(n, h, w) || total < 0) return SAMPT_ERR_ARG;
   if (n == 0) return SAMPT_OK;
   if (!offsets || !bits || !area || !status || !ws || (total > 0 && !counts)) return SAMPT_ERR_ARG;
   if (((uintptr_t)bits & 7) || ((uintptr_t)ws & 7) || ((uintptr_t)offsets & 7) || ((uintptr_t)area & 3) || ((uintptr_t)status & 3) ||
@@ -387,24 +286,24 @@ int rle_decode_bits(const unsigned* counts, const long long* offsets, int n, lon
   hipLaunchKernelGGL(k_rle_scan, dim3(n < 65535 ? n : 65535), dim3(256), 0, s, counts, offsets, n, total, (u64)h * (u64)w, (u64*)ws, area, status);
   SAMPT_CHECK_LAUNCH("rle_decode_bits scan");
   const long nwords = (long)n * nb * w;
-  hipLaunchKernelGGL(k_rle_bits, dim3(ve_blocks(nwords, 256)), dim3(256), 0, s, (const u64*)ws, offsets, (const int*)status, h, w, nb, nwords,
+  hipLaunchKernelGGL(k_rle_bits, dim3(bp_blocks(nwords, 256)), dim3(256), 0, s, (const u64*)ws, offsets, (const int*)status, h, w, nb, nwords,
                      (u64*)bits);
   SAMPT_CHECK_LAUNCH("rle_decode_bits words");
   return SAMPT_OK;
 }
 
 int bits_unpack(const unsigned long long* bits, int n, int h, int w, unsigned char* out, hipStream_t s) {
-  if (!ve_shape_ok(n, h, w)) return SAMPT_ERR_ARG;
+  if (!bp_shape_ok(n, h, w)) return SAMPT_ERR_ARG;
   if (n == 0) return SAMPT_OK;
   if (!bits || !out || ((uintptr_t)bits & 7)) return SAMPT_ERR_ARG;
   const long npix = (long)n * h * w;
-  hipLaunchKernelGGL(k_bits_unpack, dim3(ve_blocks(npix, 256)), dim3(256), 0, s, (const u64*)bits, h, w, cdiv(h, 64), npix, out);
+  hipLaunchKernelGGL(k_bits_unpack, dim3(bp_blocks(npix, 256)), dim3(256), 0, s, (const u64*)bits, h, w, cdiv(h, 64), npix, out);
   SAMPT_CHECK_LAUNCH("bits_unpack");
   return SAMPT_OK;
 }
 
 static bool si_shape_ok(int D, int G, int T, int h, int w) {
-  return D > 0 && G > 0 && T > 0 && D <= 65535 * SI_B && G <= 65535 * SI_B && ve_shape_ok(1, h, w);
+  return D > 0 && G > 0 && T > 0 && D <= 65535 * SI_B && G <= 65535 * SI_B && bp_shape_ok(1, h, w);
 }
 
 // the workgroups that share a tile's word positions: a function of the shapes alone (the sums do not depend on it)
@@ -435,7 +334,7 @@ int seq_iou_counts(const unsigned long long* dt_bits, const int* dt_area, const 
   hipLaunchKernelGGL(k_seq_iou, dim3(kb, gt, dt), dim3(256), 0, s, (const u64*)dt_bits, dt_planes, D, dt_n_planes, (const u64*)gt_bits, gt_planes,
                      G, gt_n_planes, T, wp, cpp, nchunks, dt * SI_B, gt * SI_B, (u64*)ws);
   SAMPT_CHECK_LAUNCH("seq_iou_counts");
-  hipLaunchKernelGGL(k_seq_iou_sum, dim3(ve_blocks((long)D * G, 256)), dim3(256), 0, s, (const u64*)ws, kb, dt * SI_B, gt * SI_B, dt_planes,
+  hipLaunchKernelGGL(k_seq_iou_sum, dim3(bp_blocks((long)D * G, 256)), dim3(256), 0, s, (const u64*)ws, kb, dt * SI_B, gt * SI_B, dt_planes,
                      dt_area, D, dt_n_planes, gt_planes, gt_area, G, gt_n_planes, T, counts);
   SAMPT_CHECK_LAUNCH("seq_iou_counts sum");
   return SAMPT_OK;

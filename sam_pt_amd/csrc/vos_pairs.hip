@@ -2,15 +2,15 @@
 // the expensive part of F, the disk dilation of a boundary map, depends on one mask only.  Fed to jf_counts (vos_metrics.hip) as
 // P * K items per frame, every mask is read K (or P) times and dilated as often; here every mask is read and dilated once.
 // Mask (p, t) of the seg side is item t * P + p of its source, mask (k, t) of the ann side item t * K + k; the frame's void plane
-// (optional bytes) is cleared from both.  Sources, boundary map, disk and radius range are those of vos_metrics.hip (jf_bits.h).
+// (optional bytes) is cleared from both.  Sources, boundary map, disk and radius range are those of vos_metrics.hip (bitplane.h,
+// jf_bits.h).
 //
-//   k_jfp_words   one wave per (mask, tile of 64 rows x 256 columns), the loader of k_jf_words: every pixel is read once into 64-bit
+//   k_jfp_words   one wave per (mask, tile of 64 rows x 256 columns), the tile reader of bitplane.h: every pixel is read once into 64-bit
 //                 column words; writes the mask bit-plane and the boundary bit-plane (workspace [mask][band][x]) and adds the mask's
 //                 area and boundary count to its stat pair.  Run once for the seg side and once for the ann side.
-//   k_jfp_dilate  one workgroup per (mask, band, 256 columns), one thread per column, k_jf_match's scheme: the vertical dilations
-//                 V_k of the boundary words (with the bands above and below) grow in registers, a level that some dx of the disk uses
-//                 is staged in LDS and every thread ORs the columns x +- dx of it.  The dilated map is written as a third bit-plane,
-//                 because every partner of the mask reuses it.  A tile with nothing in reach writes zeros and leaves early.
+//   k_jfp_dilate  one workgroup per (mask, band, 256 columns), one thread per column: the disk dilation of the boundary words (jf_halo /
+//                 jf_dilate of jf_bits.h).  The dilated map is written as a third bit-plane, because every partner of the mask reuses
+//                 it.  A tile with nothing in reach writes zeros and leaves early.
 //   k_jfp_pairs   a popcount GEMM over the bit words: a workgroup takes a tile of 4 x 4 pairs of one frame and a slice of the
 //                 planes' words; a thread loads word j of the 3 planes of 4 proposals and of 4 objects (24 words) and adds the
 //                 48 popcounts inter = m_p & m_k, seg_match = b_p & dil(b_k), ann_match = b_k & dil(b_p).  A word is fetched once
@@ -29,43 +29,31 @@ constexpr int JP_SLICE = 2048;               // words of a plane per workgroup o
 // tiles = n * nb * ncb in (item, band, column block) order, item = frame * per_frame + mask of the frame; the item's planes are
 // number plane0 + item of mb / bb ([.][nb][w]); stat int32 [n][2] (zeroed) = area, boundary count
 template <int KIND, bool VEC>
-__global__ __launch_bounds__(256) void k_jfp_words(JfSrc src, JfSrc vd, int per_frame, int h, int w, int nb, int ncb, long tiles, int wvec,
+__global__ __launch_bounds__(256) void k_jfp_words(BpSrc src, BpSrc vd, int per_frame, int h, int w, int nb, int ncb, long tiles, int wvec,
                                                    long plane0, u64* __restrict__ mb, u64* __restrict__ bb, int* __restrict__ stat) {
   const int lane = threadIdx.x & 63;
   const long npix = (long)h * w;
   for (long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6); t < tiles; t += (long)gridDim.x * 4) {   // wave-uniform
-    const int cb = (int)(t % ncb);
-    const long q = t / ncb;
-    const int rb = (int)(q % nb);
-    const long item = q / nb;
-    const int y0 = rb * 64, x0 = cb * 256 + lane * 4, xe = cb * 256 + 256;
+    const BpTile k = bp_tile(t, nb, ncb, lane);
     JfBits M;
-    jf_bits<KIND, VEC>(src, item, npix, y0, x0, xe, h, w, lane, M);
+    jf_bits<KIND, VEC>(src, k.item, npix, k, h, w, lane, M);
     if (vd.base) {
       JfBits V;
-      jf_bits<JF_KIND_BYTES, VEC>(vd, item / per_frame, npix, y0, x0, xe, h, w, lane, V);
+      jf_bits<BP_KIND_BYTES, VEC>(vd, k.item / per_frame, npix, k, h, w, lane, V);
       jf_clear(M, V);
     }
     u64 b[4];
-    jf_boundary(M, y0, x0, h, w, lane, b);
+    jf_boundary(M, k.y0, k.x0, h, w, lane, b);
     int area = 0, nbd = 0;
 #pragma unroll
     for (int c = 0; c < 4; ++c) area += __popcll(M.word[c]), nbd += __popcll(b[c]);
-    const long o = ((plane0 + item) * nb + rb) * (long)w + x0;
-    if (wvec) {                                                // w % 4 == 0: 32-byte aligned, x0 < w means all four columns
-      if (x0 < w) {
-        *(ulonglong2*)(mb + o) = make_ulonglong2(M.word[0], M.word[1]), *(ulonglong2*)(mb + o + 2) = make_ulonglong2(M.word[2], M.word[3]);
-        *(ulonglong2*)(bb + o) = make_ulonglong2(b[0], b[1]), *(ulonglong2*)(bb + o + 2) = make_ulonglong2(b[2], b[3]);
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (x0 + c < w) mb[o + c] = M.word[c], bb[o + c] = b[c];
-    }
-    area = jf_wave_sum(area), nbd = jf_wave_sum(nbd);
+    const long o = ((plane0 + k.item) * nb + k.rb) * (long)w + k.x0;
+    bp_store4(mb + o, M.word, k.x0, w, wvec);
+    bp_store4(bb + o, b, k.x0, w, wvec);
+    area = bp_wave_sum(area), nbd = bp_wave_sum(nbd);
     if (lane == 0) {
-      if (area) atomicAdd(stat + item * 2, area);
-      if (nbd) atomicAdd(stat + item * 2 + 1, nbd);
+      if (area) atomicAdd(stat + k.item * 2, area);
+      if (nbd) atomicAdd(stat + k.item * 2 + 1, nbd);
     }
   }
 }
@@ -76,45 +64,19 @@ __global__ __launch_bounds__(256) void k_jfp_dilate(const u64* __restrict__ bb, 
   __shared__ u64 lv[2][256 + 2 * JF_MAX_R];
   const int tid = threadIdx.x;
   for (long t = blockIdx.x; t < tiles; t += gridDim.x) {       // block-uniform
-    const int cb = (int)(t % ncb);
-    const long q = t / ncb;
-    const int rb = (int)(q % nb);
-    const long plane = q / nb;
-    const u64* src = bb + plane * nb * (long)w;
-    const int x = cb * 256 + tid;
-    u64 up[2], mid[2], dn[2], V[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {                              // halo column tid + 256 i of 256 + 2 r = image column xx
-      const int hc = tid + i * 256, xx = cb * 256 - r + hc;
-      const bool ok = hc < 256 + 2 * r && xx >= 0 && xx < w;
-      mid[i] = ok ? src[(long)rb * w + xx] : 0ull;
-      up[i] = ok && rb > 0 ? src[(long)(rb - 1) * w + xx] : 0ull;
-      dn[i] = ok && rb + 1 < nb ? src[(long)(rb + 1) * w + xx] : 0ull;
-      V[i] = mid[i];
-    }
-    u64* dst = db + (plane * nb + rb) * (long)w;
+    const BpTile k = bp_tile(t, nb, ncb, 0);                   // k.item = the plane
+    const int x = k.cb * 256 + tid;
+    u64 up[2], mid[2], dn[2];
+    jf_halo(bb + k.item * nb * (long)w, k, nb, w, r, tid, mid, up, dn);
+    u64* dst = db + (k.item * nb + k.rb) * (long)w;
     const u64 any = mid[0] | mid[1] | up[0] | up[1] | dn[0] | dn[1];
-    if (!__syncthreads_or(any != 0ull)) {                      // (also: the previous tile's readers of lv are done)
+    // the barrier that jf_dilate asks for: past it, the previous tile's readers of lv are done
+    if (!__syncthreads_or(any != 0ull)) {
       if (x < w) dst[x] = 0ull;
       continue;
     }
-    u64 D = 0;
-    int p = 0;
-    for (int k = 0; k <= r; ++k) {
-      if (k > 0) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)                            // rows y - k and y + k (k = 64: the neighbouring bands themselves)
-          V[i] |= k < 64 ? (mid[i] << k) | (up[i] >> (64 - k)) | (mid[i] >> k) | (dn[i] << (64 - k)) : up[i] | dn[i];
-      }
-      const int lo = disk.lo[k], hi = disk.hi[k];
-      if (lo > hi) continue;                                   // no dx has this half-height
-      lv[p][tid] = V[0];
-      if (tid + 256 < 256 + 2 * r) lv[p][tid + 256] = V[1];
-      __syncthreads();                                         // (the buffer written two levels on is free: its readers passed here)
-      for (int dx = lo; dx <= hi; ++dx) D |= lv[p][tid + r - dx] | lv[p][tid + r + dx];
-      p ^= 1;
-    }
-    const int rows = h - rb * 64 < 64 ? h - rb * 64 : 64;      // the bits of rows >= h stay 0, as in every bit-plane
+    const u64 D = jf_dilate(mid, up, dn, r, disk, lv, tid);
+    const int rows = h - k.y0 < 64 ? h - k.y0 : 64;            // the bits of rows >= h stay 0, as in every bit-plane
     if (x < w) dst[x] = rows == 64 ? D : D & ((1ull << rows) - 1ull);
   }
 }
@@ -181,7 +143,7 @@ __global__ __launch_bounds__(256) void k_jfp_pairs(const u64* __restrict__ mb, c
       for (int c = 0; c < JP_TK; ++c)
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-          const int v = jf_wave_sum(acc[a][c][i]);
+          const int v = bp_wave_sum(acc[a][c][i]);
           if ((tid & 63) == 0 && v) atomicAdd(&red[(a * JP_TK + c) * 3 + i], v);
         }
     __syncthreads();
@@ -195,7 +157,7 @@ __global__ __launch_bounds__(256) void k_jfp_pairs(const u64* __restrict__ mb, c
 
 // --------------------------------------------------------------------------------------------------------------------
 static bool jfp_shape_ok(int P, int K, int T, int h, int w, int r) {
-  return P > 0 && K > 0 && T > 0 && h > 0 && w > 0 && (long)h * w < (1L << 31) && r >= 0 && r <= JF_MAX_R && (long)P * T < (1L << 31) &&
+  return P > 0 && K > 0 && T > 0 && bp_shape_ok(T, h, w) && r >= 0 && r <= JF_MAX_R && (long)P * T < (1L << 31) &&
          (long)K * T < (1L << 31) && (long)P * K * T * 3 < (1L << 31);
 }
 
@@ -210,14 +172,10 @@ int jf_pairs_counts(const void* seg, int seg_kind, float seg_thr, const int* seg
                     size_t ws_bytes, hipStream_t s) {
   const int P = n_seg, K = n_ann, T = n_frames, r = radius;
   if (!jfp_shape_ok(P, K, T, h, w, r)) return SAMPT_ERR_ARG;
-  JfSrc S, A, V;
-  if (!jf_src(S, seg, seg_kind, seg_thr, seg_values, seg_planes, w)) return SAMPT_ERR_ARG;
-  if (!jf_src(A, ann, ann_kind, ann_thr, ann_values, ann_planes, w)) return SAMPT_ERR_ARG;
-  if (void_px) {
-    jf_src(V, void_px, JF_KIND_BYTES, 0.f, nullptr, void_planes, w);
-  } else {
-    V.base = nullptr, V.planes = nullptr, V.values = nullptr, V.thr = 0.f, V.kind = JF_KIND_BYTES;
-  }
+  BpSrc S, A, V = bp_no_source();
+  if (!bp_source(S, seg, seg_kind, seg_thr, seg_values, seg_planes)) return SAMPT_ERR_ARG;
+  if (!bp_source(A, ann, ann_kind, ann_thr, ann_values, ann_planes)) return SAMPT_ERR_ARG;
+  if (void_px) bp_source(V, void_px, BP_KIND_BYTES, 0.f, nullptr, void_planes);
   if (!pair_out || !seg_stat || !ann_stat || !ws || ((uintptr_t)ws & 15)) return SAMPT_ERR_ARG;
   if (((uintptr_t)pair_out & 3) || ((uintptr_t)seg_stat & 3) || ((uintptr_t)ann_stat & 3)) return SAMPT_ERR_ARG;
   if (ws_bytes < jf_pairs_workspace_bytes(P, K, T, h, w, r)) return SAMPT_ERR_WORKSPACE;
@@ -234,25 +192,24 @@ int jf_pairs_counts(const void* seg, int seg_kind, float seg_thr, const int* seg
   u64* mb = (u64*)ws;
   u64* bb = mb + planes * W;
   u64* db = bb + planes * W;
-  typedef void (*words_fn)(JfSrc, JfSrc, int, int, int, int, int, long, int, long, u64*, u64*, int*);
+  typedef void (*words_fn)(BpSrc, BpSrc, int, int, int, int, int, long, int, long, u64*, u64*, int*);
   static const words_fn table[3][2] = {{k_jfp_words<0, false>, k_jfp_words<0, true>},
                                        {k_jfp_words<1, false>, k_jfp_words<1, true>},
                                        {k_jfp_words<2, false>, k_jfp_words<2, true>}};
   for (int side = 0; side < 2; ++side) {
     const int per = side ? K : P;
     const long tiles = (long)per * T * nb * ncb;
-    const int blocks = (int)((tiles + 3) / 4 < JF_MAX_BLOCKS ? (tiles + 3) / 4 : JF_MAX_BLOCKS);
-    hipLaunchKernelGGL(table[side ? ann_kind : seg_kind][w >= 4 ? 1 : 0], dim3(blocks), dim3(256), 0, s, side ? A : S, V, per, h, w, nb, ncb,
+    hipLaunchKernelGGL(table[side ? ann_kind : seg_kind][w >= 4 ? 1 : 0], dim3(bp_blocks(tiles, 4)), dim3(256), 0, s, side ? A : S, V, per, h, w, nb, ncb,
                        tiles, w % 4 == 0 ? 1 : 0, side ? (long)P * T : 0L, mb, bb, side ? ann_stat : seg_stat);
     SAMPT_CHECK_LAUNCH("jf_pairs_counts words");
   }
   const long dtiles = planes * nb * ncb;
-  hipLaunchKernelGGL(k_jfp_dilate, dim3((int)(dtiles < JF_MAX_BLOCKS ? dtiles : JF_MAX_BLOCKS)), dim3(256), 0, s, (const u64*)bb, db, h, w, nb,
+  hipLaunchKernelGGL(k_jfp_dilate, dim3(bp_blocks(dtiles, 1)), dim3(256), 0, s, (const u64*)bb, db, h, w, nb,
                      ncb, r, disk, dtiles);
   SAMPT_CHECK_LAUNCH("jf_pairs_counts dilate");
   const int ptiles = cdiv(P, JP_TP), ktiles = cdiv(K, JP_TK), nsl = (int)((W + JP_SLICE - 1) / JP_SLICE);
   const long ptl = (long)T * ptiles * ktiles * nsl;
-  hipLaunchKernelGGL(k_jfp_pairs, dim3((int)(ptl < JF_MAX_BLOCKS ? ptl : JF_MAX_BLOCKS)), dim3(256), 0, s, (const u64*)mb, (const u64*)bb,
+  hipLaunchKernelGGL(k_jfp_pairs, dim3(bp_blocks(ptl, 1)), dim3(256), 0, s, (const u64*)mb, (const u64*)bb,
                      (const u64*)db, P, K, T, W, ptiles, ktiles, nsl, ptl, pair_out);
   SAMPT_CHECK_LAUNCH("jf_pairs_counts pairs");
   return SAMPT_OK;

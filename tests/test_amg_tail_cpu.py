@@ -38,6 +38,17 @@ def seeded_masks(n: int, h: int, w: int, seed: int) -> torch.Tensor:
     return m
 
 
+def offset_view(x: torch.Tensor, dev) -> torch.Tensor:
+    """x on the HIP device ``dev``, as a view that starts one element into its storage: 1 byte (bool, uint8) or 4 bytes (float32)
+    past an allocation's alignment, so that no row and no 4-pixel load is aligned (the device allocator aligns to 16 bytes and
+    more; the assert below holds the helper to that)."""
+    flat = torch.zeros(x.numel() + 1, dtype=x.dtype, device=dev)
+    flat[1:] = x.flatten().to(dev)
+    view = flat[1:].view(x.shape)
+    assert view.data_ptr() % 16 == x.element_size() and view.is_contiguous()
+    return view
+
+
 def tie_mask() -> np.ndarray:
     """6 x 6, two 2-px components: with every component small the first in raster order survives."""
     m = np.zeros((6, 6), dtype=bool)

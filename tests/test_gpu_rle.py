@@ -38,8 +38,8 @@ def _check(dev, masks: torch.Tensor, what="", **kw):
 
 
 # ---------------------------------------------------------------------------------------------------------- byte input
-@pytest.mark.parametrize("shape", [(1, 1, 2), (63, 5, 3), (64, 4, 3), (65, 7, 3), (130, 33, 3), (7, 300, 2), (300, 7, 2), (96, 128, 12),
-                                   (576, 1024, 4)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("shape", [(1, 1, 2), (63, 5, 3), (64, 4, 3), (65, 7, 3), (130, 33, 3), (65, 261, 3), (7, 300, 2), (300, 7, 2),
+                                   (96, 128, 12), (576, 1024, 4)], ids=lambda s: f"{s[0]}x{s[1]}")
 def test_seeded_stacks_vs_host(dev, shape):
     h, w, n = shape
     masks = seeded_masks(n, h, w, seed=300 + h + w)
@@ -75,6 +75,7 @@ def test_degenerate_and_structured_masks(dev):
     cb = _check(dev, checkerboard()[None], "checkerboard")
     assert len(cb[0]["counts"]) == 938 and sum(cb[0]["counts"]) == 960
     _check(dev, checkerboard(64, 256)[None], "checkerboard 64x256")   # every bit of every word of a full tile
+    _check(dev, checkerboard(64, 261)[None], "checkerboard 64x261")   # ... and of the lane that loads a row's last 4 pixels
     _check(dev, torch.stack([column_ends_set(), ~column_ends_set()]), "column ends")
     for hh in (128, 129):
         _check(dev, torch.stack([column_ends_set(hh, 8), ~column_ends_set(hh, 8)]), f"column ends, aligned, h = {hh}")
@@ -89,7 +90,7 @@ def test_unaligned_base(dev):
     assert view.data_ptr() % 4 != 0
     got, areas = A.rle_encode_device(view)
     assert got == A.mask_to_rle(stack[1:].cpu()) and areas.cpu().tolist() == stack[1:].flatten(-2).sum(-1).cpu().tolist()
-    wide = seeded_masks(3, 33, 12, seed=22).to(dev)                  # w % 4 == 0 and an odd byte offset: the element path
+    wide = seeded_masks(3, 33, 12, seed=22).to(dev)                  # w % 4 == 0 and an odd byte offset: unaligned 4-pixel loads
     flat = torch.zeros(3 * 33 * 12 + 1, dtype=torch.bool, device=dev)
     flat[1:] = wide.flatten()
     off = flat[1:].view(3, 33, 12)
@@ -99,7 +100,7 @@ def test_unaligned_base(dev):
 
 
 # --------------------------------------------------------------------------------------------------------- float input
-@pytest.mark.parametrize("shape", [(65, 7), (96, 128)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("shape", [(65, 7), (96, 128), (130, 33), (65, 261)], ids=lambda s: f"{s[0]}x{s[1]}")
 def test_float_input_with_threshold(dev, shape):
     h, w = shape
     g = torch.Generator().manual_seed(31 + h)

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from sam_pt_amd import vos_metrics as VM
-from tests.test_amg_tail_cpu import seeded_masks
+from tests.test_amg_tail_cpu import offset_view, seeded_masks
 from tests.test_vos_metrics_cpu import seeded_pair
 
 pytestmark = pytest.mark.gpu
@@ -180,6 +180,32 @@ def test_all_input_kinds_agree(dev, shape):
         VM.jf_counts_device(d(pred), d(gt), seg_values=values, seg_planes=planes + 1, ann_values=values, ann_planes=planes)
     with pytest.raises(_lib.SamptError):
         VM.jf_counts_device(d(pred), d(gt), seg_values=values + 300, seg_planes=planes, ann_values=values, ann_planes=planes)
+
+
+# ------------------------------------------------------------------------------------------------------ unaligned bases
+@pytest.mark.parametrize("shape", ((65, 7), (70, 261)), ids=lambda s: f"{s[0]}x{s[1]}")
+def test_unaligned_bases(dev, shape):
+    h, w = shape
+    n, r, thr = 3, 3, 0.25
+    pred, gt = index_maps(n, 2, h, w, seed=41), index_maps(n, 2, h, w, seed=42)
+    values = np.array([1, 2, 1])
+    ids = torch.as_tensor(values, dtype=torch.uint8)[:, None, None]
+    seg, ann = pred == ids, gt == ids                                     # item i: value values[i] of plane i
+    void = seeded_masks(n, h, w, seed=43) & seeded_masks(n, h, w, seed=44)
+    exp = VM.jf_counts(seg, ann, void, radius=r)
+    assert exp[:, 1:4].min() > 0 and exp[:, 0].max() > 0 and not np.array_equal(exp, VM.jf_counts(seg, ann, radius=r))
+    v = offset_view(void, dev)
+    assert_counts(VM.jf_counts_device(offset_view(seg, dev), offset_view(ann, dev), v, radius=r), exp, "bytes")
+    assert_counts(VM.jf_counts_device(offset_view(pred, dev), offset_view(gt, dev), v, radius=r, seg_values=values, ann_values=values),
+                  exp, "index maps")
+    g = torch.Generator().manual_seed(45)
+    logit = lambda m: torch.where(m, thr + 0.01 + torch.rand(m.shape, generator=g), thr - torch.rand(m.shape, generator=g))
+    fs, fa = logit(seg), logit(ann)
+    assert torch.equal(fs > thr, seg) and torch.equal(fa > thr, ann)
+    assert_counts(VM.jf_counts_device(offset_view(fs, dev), offset_view(fa, dev), v, radius=r, seg_threshold=thr, ann_threshold=thr),
+                  exp, "f32")
+    assert_counts(VM.jf_counts_device(offset_view(fs, dev), offset_view(gt, dev), v, radius=r, seg_threshold=thr, ann_values=values),
+                  exp, "f32 seg, index ann")
 
 
 # ---------------------------------------------------------------------------------------------------- sequence protocol

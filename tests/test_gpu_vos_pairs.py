@@ -13,7 +13,7 @@ import torch
 
 from sam_pt_amd import _lib
 from sam_pt_amd import vos_metrics as VM
-from tests.test_amg_tail_cpu import seeded_masks
+from tests.test_amg_tail_cpu import offset_view, seeded_masks
 from tests.test_vos_pairs_cpu import sequence
 
 pytestmark = pytest.mark.gpu
@@ -116,6 +116,21 @@ def test_sources(dev, shape, source, with_void):
         mixed = VM.jf_pairs_counts_device(smap.to(dev), A.to(dev), v, radius=1, seg_values=np.arange(1, P + 1), return_stats=True)
         assert torch.equal(mixed[1], got[1]) and torch.equal(mixed[2], torch.as_tensor(host_planes(h, w, P, K, T, 1, with_void)[2]).to(dev))
     assert_same(got, exp, f"{shape} {source} void={with_void}")
+
+
+@pytest.mark.parametrize("shape", ((65, 7), (70, 261)), ids=lambda s: f"{s[0]}x{s[1]}")
+def test_unaligned_bases(dev, shape):
+    """Every source one element into its storage: no row and no 4-pixel load is aligned."""
+    (h, w), (P, K, T) = shape, PKT[3]
+    S, A, void, f, smap, amap = inputs(h, w, P, K, T)
+    v = offset_view(void, dev)
+    exp = host_planes(h, w, P, K, T, 3, True)
+    assert_same(VM.jf_pairs_counts_device(offset_view(S, dev), offset_view(A, dev), v, radius=3, return_stats=True), exp, f"{shape} bytes")
+    assert_same(VM.jf_pairs_counts_device(offset_view(f, dev), offset_view(A, dev), v, radius=3, seg_threshold=THR, return_stats=True), exp,
+                f"{shape} f32")
+    kw = dict(radius=3, seg_values=np.arange(1, P + 1), ann_values=2 * np.arange(K) + 3, return_stats=True)
+    assert_same(VM.jf_pairs_counts_device(offset_view(smap, dev), offset_view(amap, dev), v, **kw),
+                VM.jf_pairs_counts(smap.numpy(), amap.numpy(), void.numpy(), **kw), f"{shape} index maps")
 
 
 @pytest.mark.parametrize("shape", ((5, 3), (130, 90)), ids=lambda s: f"{s[0]}x{s[1]}")
