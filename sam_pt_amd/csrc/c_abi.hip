@@ -7,7 +7,7 @@
 #include <unordered_map>
 
 #include "../../include/sampt_hip.h"
-#include "engine.h"
+#include "engine_layers.h"
 
 namespace sampt {
 static thread_local std::string g_err;
@@ -1077,21 +1077,16 @@ int sampt_bbox_from_logits(const float* logits, int h, int w, int32_t* bbox_stat
 // ------------------------------------------------------------------------------------------- kernel-level
 int sampt_gemm(int dtype, const void* A, const void* W, const float* bias, const float* res, void* C, int M, int N, int K,
                int act, float alpha, sampt_stream_t stream) {
-  GemmP p;
-  p.A = A, p.W = W, p.bias = bias, p.res = res, p.C = C;
-  p.M = M, p.N = N, p.K = K, p.lda = K, p.ldw = K, p.ldc = N, p.ldr = N, p.act = act, p.alpha = alpha;
-  p.out_f16 = dtype == 2;
+  GemmP p = gemm_linear(A, K, W, bias, C, N, M, N, K, act, res);
+  p.alpha = alpha, p.out_f16 = dtype == 2;
   return dtype == 0 ? gemm_f32(p, (hipStream_t)stream) : gemm_f16(p, (hipStream_t)stream);
 }
 
 int sampt_gemm_ex(int dtype, const void* A, const void* W, const float* bias, const float* res, void* C, int M, int N, int K,
                   int act, float alpha, const int32_t* rowmap, const int32_t* a_rowmap, int res_mod, int ldr,
                   sampt_stream_t stream) {
-  GemmP p;
-  p.A = A, p.W = W, p.bias = bias, p.res = res, p.C = C, p.rowmap = rowmap, p.a_rowmap = a_rowmap;
-  p.M = M, p.N = N, p.K = K, p.lda = K, p.ldw = K, p.ldc = N, p.ldr = ldr > 0 ? ldr : N, p.act = act, p.alpha = alpha;
-  p.res_mod = res_mod;
-  p.out_f16 = dtype == 2;
+  GemmP p = gemm_linear(A, K, W, bias, C, N, M, N, K, act, res, ldr > 0 ? ldr : N, res_mod);
+  p.alpha = alpha, p.rowmap = rowmap, p.a_rowmap = a_rowmap, p.out_f16 = dtype == 2;
   if (dtype == 3 || dtype == 4) {   // x3 rows in (A, W: 2K halves per row), f32 or x3 rows out
     p.x3 = 1, p.K = 2 * K, p.lda = 2 * K, p.ldw = 2 * K;
     if (dtype == 4) p.out_f16 = 2, p.ldc = 2 * N;
@@ -1135,14 +1130,10 @@ int sampt_split_rows_x3(const float* x, void* y, int M, int K, sampt_stream_t st
 
 int sampt_conv2d_nhwc(int dtype, const void* x, const void* w, const float* bias, float* y, int n, int H, int W, int Cin,
                       int Cout, int KH, int KW, int stride, int pad, sampt_stream_t stream) {
-  GemmP p;
-  p.OH = (H + 2 * pad - KH) / stride + 1, p.OW = (W + 2 * pad - KW) / stride + 1;
-  p.A = x, p.W = w, p.bias = bias, p.C = y;
-  p.M = n * p.OH * p.OW, p.N = Cout, p.K = KH * KW * Cin, p.ldw = p.K, p.ldc = Cout;
-  p.conv = 1, p.cH = H, p.cW = W, p.cC = Cin, p.KH = KH, p.KW = KW, p.cstride = stride, p.cpad = pad;
+  const ConvW c{(const float*)w, bias, nullptr, Cin, Cout, KH, KW, stride, pad, pad};
+  GemmP p = gemm_conv(c, x, n, H, W, y);
   if (dtype == 3 || dtype == 4) {
-    p.W_lo = (const half_t*)w + (size_t)Cout * p.K;
-    p.alpha = 1.0f / (float)(1 << F16X3_WSHIFT);
+    gemm_split_planes(p, (const half_t*)w);
     if (dtype == 4) p.A_lo = (const half_t*)x + (size_t)n * H * W * Cin;   // activations pre-split: [2][n][H][W][Cin] halves
     return conv_f16x3(p, (hipStream_t)stream);
   }
@@ -1157,11 +1148,8 @@ int sampt_gemm_x3_rows(const float* A, const void* w_hl, const float* bias, cons
 int sampt_gemm_x3_rows_epi(const float* A, const void* w_hl, const float* bias, const float* res, int res_mod, float* C, int M, int N,
                            int K, int act, int shuf_g, int epi, const float* epi_a, const float* epi_b, float epi_eps, int epi_ld,
                            sampt_stream_t stream) {
-  GemmP p;
-  p.A = A, p.W = w_hl, p.W_lo = (const half_t*)w_hl + (size_t)N * K, p.bias = bias, p.res = res, p.res_mod = res_mod, p.C = C;
-  p.alpha = 1.0f / (float)(1 << F16X3_WSHIFT), p.act = act;
-  p.M = M, p.N = N, p.K = K, p.ldw = K, p.ldc = epi == 2 ? 1 : (shuf_g ? N / 4 : N), p.ldr = shuf_g ? N / 4 : N;
-  p.conv = 1, p.cH = M, p.cW = 1, p.cC = K, p.KH = 1, p.KW = 1, p.cstride = 1, p.cpad = 0, p.OH = M, p.OW = 1;
+  GemmP p = gemm_linear(A, K, nullptr, bias, C, epi == 2 ? 1 : (shuf_g ? N / 4 : N), M, N, K, act, res, shuf_g ? N / 4 : N, res_mod);
+  gemm_split_planes(p, (const half_t*)w_hl);
   p.shuf_g = shuf_g, p.shuf_n = shuf_g ? N / 4 : 0;
   p.epi = epi, p.epi_a = epi_a, p.epi_b = epi_b, p.epi_eps = epi_eps, p.epi_ld = epi_ld;
   if (epi) {       // the fused tails exist in the weights-resident kernel only: refuse rather than compute something else
@@ -1194,12 +1182,10 @@ int sampt_conv_stem7x7(const float* x_nhwc4, const float* w, const float* bias, 
 
 int sampt_conv3x3_planes_instnorm_stats(const void* x_hl, const void* w_hl, const float* bias, float* y, int n, int H, int W, int Cin,
                                         int Cout, float eps, float* mean_rstd, void* ws, size_t ws_bytes, sampt_stream_t stream) {
-  GemmP p;
-  p.OH = H, p.OW = W;
-  p.A = x_hl, p.A_lo = (const half_t*)x_hl + (size_t)n * H * W * Cin, p.W = w_hl, p.W_lo = (const half_t*)w_hl + (size_t)Cout * 9 * Cin;
-  p.bias = bias, p.C = y, p.alpha = 1.0f / (float)(1 << F16X3_WSHIFT);
-  p.M = n * H * W, p.N = Cout, p.K = 9 * Cin, p.ldw = p.K, p.ldc = Cout;
-  p.conv = 1, p.cH = H, p.cW = W, p.cC = Cin, p.KH = 3, p.KW = 3, p.cstride = 1, p.cpad = 1;
+  const ConvW c{nullptr, bias, (const half_t*)w_hl, Cin, Cout, 3, 3, 1, 1, 1};
+  GemmP p = gemm_conv(c, x_hl, n, H, W, y);
+  gemm_split_planes(p, c.w_hl);
+  p.A_lo = (const half_t*)x_hl + (size_t)n * H * W * Cin;
   if (!conv3x3_halo_eligible(p)) return fail(SAMPT_ERR_UNSUPPORTED, "sampt_conv3x3_planes_instnorm_stats: Cin % 32, Cout % 4");
   const int chunks = conv3x3_halo_tiles(p);
   if (ws_bytes < (size_t)n * chunks * Cout * 2 * sizeof(double)) return SAMPT_ERR_WORKSPACE;

@@ -45,19 +45,23 @@ struct Arena {
 };
 
 // -------------------------------------------------------------------------------------------------
+// The two layer descriptors of every engine; engine_layers.h loads them and turns them into launches.
 struct ConvW {
   const float* w = nullptr;  // [Cout][KH*KW*Cin] (ci fastest), f32
   const float* b = nullptr;
   const half_t* w_hl = nullptr;  // optional: the same weights split into fp16 planes [2][Cout][K] (conv_f16x3.hip)
-  int cin = 0, cout = 0, k = 0, stride = 1, pad = 0;
+  int cin = 0, cout = 0, kh = 1, kw = 1, stride = 1, ph = 0, pw = 0;
+};
+struct LinearW {
+  const float *w = nullptr, *b = nullptr;   // [N][K], [N]
+  int n = 0, k = 0;
 };
 
 struct PipsEngine {
   int S = 8, stride = 4;
   int frames_f32 = 0;   // fnet input: 0 = uint8 frames, 1 = float frames in [0, 255] (PIPS++ with image_size)
   ConvW stem, conv2, conv3;
-  ConvW blk[4][2][3];  // [layer][block][conv1, conv2, downsample]
-  bool has_down[4][2] = {};
+  ConvW blk[4][2][3];  // [layer][block][conv1, conv2, downsample (where conv1 has a stride)]
   // mixer
   const float *in_w, *in_b, *head_w, *head_b, *oln_w, *oln_b;
   struct MixBlk {
@@ -94,11 +98,7 @@ struct PipsEngine {
 struct Pips2Engine {
   PipsEngine enc;                      // fnet only
   int stride = 8;
-  struct Conv1 {
-    const float *w, *b;                // [Cout][3*Cin] (tap-major, ci fastest), [Cout]
-    int cin, cout;
-  };
-  Conv1 first, blk[8][2];
+  ConvW first, blk[8][2];              // Conv1d(k = 3) as 3 x 1 convolutions: [Cout][3*Cin] (tap-major, ci fastest), [Cout]
   const float *dense_w, *dense_b, *omega;
   std::string error;
 
@@ -138,16 +138,11 @@ struct CotEngine {
 // RAFT (sam_pt/point_tracker/raft/): both encoders once per frame, then every pair-direction of the clip through the
 // 4-level all-pairs correlation and `iters` recurrent updates, a chunk of pairs at a time.  All convolutions run on the
 // exact-f32 implicit GEMM; weights as packed by pack.pack_raft (cnet's BatchNorms folded into its convolutions).
-struct RaftConv {
-  const float *w = nullptr, *b = nullptr;   // [Cout][KH*KW*Cin] (ci fastest), [Cout]
-  int cin = 0, cout = 0, kh = 1, kw = 1, stride = 1, ph = 0, pw = 0;
-};
-
 struct RaftEngine {
   struct Enc {
-    RaftConv stem, blk[3][2][3], out;       // [layer][block][conv1, conv2, downsample]
+    ConvW stem, blk[3][2][3], out;          // [layer][block][conv1, conv2, downsample]
   } fnet, cnet;
-  RaftConv convc1, convc2, convf2, conv, zr[2], q[2], fh1, fh2, mask0, mask2;
+  ConvW convc1, convc2, convf2, conv, zr[2], q[2], fh1, fh2, mask0, mask2;
   const float *convf1_w = nullptr, *convf1_b = nullptr;   // [98][128], [128]
   std::string error;
 
@@ -166,20 +161,16 @@ int raft_corr_levels(const float* fmap1, long s1, const float* const pooled[4], 
 
 // -------------------------------------------------------------------------------------------------
 // SuperPoint + SuperGlue (engine_superglue.hip).  Weights after sam_pt_amd.pack.pack_superglue.
-struct SgLinear {
-  const float *w = nullptr, *b = nullptr;   // [N][K], [N]
-  int n = 0, k = 0;
-};
 struct SgDetectCfg {
   int nms_radius = 4, border = 4, cap = 0;
   float threshold = 0.005f;
 };
 struct SgEngine {
-  RaftConv sp[8], convPa, convPb, convDa, convDb;    // convPb: 65 outputs zero-padded to 68
-  SgLinear kenc[5];
-  struct Layer { SgLinear qkv, merge, mlp0, mlp1; } gnn[18];
+  ConvW sp[8], convPa, convPb, convDa, convDb;    // convPb: 65 outputs zero-padded to 68
+  LinearW kenc[5];
+  struct Layer { LinearW qkv, merge, mlp0, mlp1; } gnn[18];
   int cross[18];
-  SgLinear final_proj;
+  LinearW final_proj;
   const float* bin_score = nullptr;
   std::string error;
 

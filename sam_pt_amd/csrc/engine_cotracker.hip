@@ -5,7 +5,7 @@
 //
 // Reference call site: sam_pt/point_tracker/cotracker/tracker.py:104 (`self.model(rgbs, queries, iters=6)`) and :159-161
 // (time-flipped pass); the model itself is third-party (co-tracker @ 4f297a9).
-#include "engine.h"
+#include "engine_layers.h"
 
 namespace sampt {
 
@@ -40,22 +40,6 @@ int CotEngine::init(const WeightMap& w) {
   return SAMPT_OK;
 }
 
-namespace {
-struct Lin {
-  hipStream_t s;
-  float* skws;
-  size_t skn;
-  int operator()(const float* A, int M, int K, const float* W, const float* b, float* C, int N, int act = ACT_NONE,
-                 const float* res = nullptr) const {
-    GemmP p;
-    p.A = A, p.W = W, p.bias = b, p.C = C, p.res = res;
-    p.splitk_ws = skws, p.splitk_ws_floats = skn;
-    p.M = M, p.N = N, p.K = K, p.lda = K, p.ldw = K, p.ldc = N, p.ldr = N, p.act = act;
-    return gemm_f32(p, s);
-  }
-};
-}  // namespace
-
 int CotEngine::track(const PyramidLevels& pyr, int T, const int* frame_map, int n, const int* qt_host, const int* qt_dev,
                      const float* qxy, const float* pos_x, const float* pos_y, int iters, float* traj_out, float* vis_out,
                      Arena& ws, hipStream_t s) {
@@ -87,7 +71,8 @@ int CotEngine::track(const PyramidLevels& pyr, int T, const int* frame_map, int 
   for (int i = 1; i < n; ++i)
     if (qt_host[i] < qt_host[i - 1]) return SAMPT_ERR_ARG;          // points sorted by query frame (CoTracker.forward)
   if (qt_host[0] < 0 || qt_host[n - 1] >= T) return SAMPT_ERR_ARG;
-  const Lin lin{s, skws, skn};
+  auto lin = [&](const float* A, int M, int K, const float* W, const float* b, float* C, int N, int act = ACT_NONE,
+                 const float* res = nullptr) { return run_linear(A, K, W, b, C, N, M, N, K, act, res, N, s, skws, skn); };
   SAMPT_TRY(cot_prepare(qxy, qt_dev, frame_map, (float)stride, n, T, xy0, fidx_pt, traj_out, vis_out, s));
   // feature of every point at its own query frame and position (bilinear_sample2d on the stride-4 map)
   SAMPT_TRY(pips_sample_feat(pyr.base[0], pyr.H[0], pyr.W[0], 128, fidx_pt, xy0, n, feat_init, s));

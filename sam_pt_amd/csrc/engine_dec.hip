@@ -10,7 +10,7 @@
 //     sequence that depends only on the token count.
 // `decode_points` is the automatic mask generator's step: n point prompts against ONE image as one such batch, the
 // prompt-independent image work done once, every mask of a prompt from one pass over its upscaled map, low-res output only.
-#include "engine.h"
+#include "engine_layers.h"
 
 namespace sampt {
 
@@ -115,16 +115,12 @@ struct L {
   const std::unordered_map<const float*, const half_t*>* w_hl = nullptr;
   int lin(const float* A, int M, int K, const float* W, const float* b, float* C, int N, int act = ACT_NONE,
           const float* res = nullptr, int lda = 0, int res_mod = 0, int ldc = 0) const {
-    GemmP p;
-    p.A = A, p.W = W, p.bias = b, p.C = C, p.res = res, p.res_mod = res_mod;   // res_mod: the residual is a block of res_mod rows, broadcast
-    p.M = M, p.N = N, p.K = K, p.lda = lda ? lda : K, p.ldw = K, p.ldc = ldc ? ldc : N, p.ldr = N, p.act = act;
+    GemmP p = gemm_linear(A, lda ? lda : K, W, b, C, ldc ? ldc : N, M, N, K, act, res, N, res_mod);   // res_mod: the residual is a block of res_mod rows, broadcast
     p.splitk_ws = skws, p.splitk_ws_floats = skn;
     if (w_hl && M >= 2048 && !lda && !ldc && K % 32 == 0 && N % 4 == 0) {     // image-token projections, split-fp16 planes packed
       auto it = w_hl->find(W);
       if (it != w_hl->end()) {
-        p.W = it->second, p.W_lo = it->second + (size_t)N * K;
-        p.alpha = 1.0f / (float)(1 << F16X3_WSHIFT);
-        p.conv = 1, p.cH = M, p.cW = 1, p.cC = K, p.KH = 1, p.KW = 1, p.cstride = 1, p.cpad = 0, p.OH = M, p.OW = 1;
+        gemm_split_planes(p, it->second);
         p.splitk_ws = nullptr, p.splitk_ws_floats = 0;
         return conv_f16x3(p, s);
       }
@@ -143,15 +139,11 @@ struct Bufs {
 
 // fused image-side projection: out [M][f.n] = A W^T + b + pe[row % P]   (see DecEngine::FusedProj)
 static int fused_proj(const L& l, const DecEngine::FusedProj& f, const float* A, long M, int C, int P, float* out) {
-  GemmP p;
-  p.A = A, p.bias = f.b, p.C = out, p.res = f.pe, p.res_mod = P;
-  p.M = (int)M, p.N = f.n, p.K = C, p.lda = C, p.ldw = C, p.ldc = f.n, p.ldr = f.n;
+  GemmP p = gemm_linear(A, C, f.w, f.b, out, f.n, (int)M, f.n, C, ACT_NONE, f.pe, f.n, P);
   if (f.hl && C % 32 == 0) {
-    p.W = f.hl, p.W_lo = f.hl + (size_t)f.n * C, p.alpha = 1.0f / (float)(1 << F16X3_WSHIFT);
-    p.conv = 1, p.cH = (int)M, p.cW = 1, p.cC = C, p.KH = 1, p.KW = 1, p.cstride = 1, p.cpad = 0, p.OH = (int)M, p.OW = 1;
+    gemm_split_planes(p, f.hl);
     return conv_f16x3(p, l.s);
   }
-  p.W = f.w;
   return gemm_f32(p, l.s);
 }
 
@@ -161,11 +153,8 @@ static int attn_tail(const L& l, const DecEngine::Attn& a, int C, long rows, con
   if (l.w_hl && resid && g_gemm_x3_wres && g_gemm_x3_epi) {      // image-token side at scale: projection + residual + LayerNorm in one kernel
     auto it = l.w_hl->find(a.ow);
     if (it != l.w_hl->end()) {
-      GemmP p;
-      p.A = att, p.W = it->second, p.W_lo = it->second + (size_t)C * a.inner, p.bias = a.ob, p.C = out, p.res = resid;
-      p.M = (int)rows, p.N = C, p.K = a.inner, p.ldw = a.inner, p.ldc = C, p.ldr = C;
-      p.alpha = 1.0f / (float)(1 << F16X3_WSHIFT);
-      p.conv = 1, p.cH = (int)rows, p.cW = 1, p.cC = a.inner, p.KH = 1, p.KW = 1, p.cstride = 1, p.cpad = 0, p.OH = (int)rows, p.OW = 1;
+      GemmP p = gemm_linear(att, a.inner, a.ow, a.ob, out, C, (int)rows, C, a.inner, ACT_NONE, resid, C);
+      gemm_split_planes(p, it->second);
       p.epi = 3, p.epi_a = lnw, p.epi_b = lnb, p.epi_eps = 1e-5f;
       if (gemm_x3_wres_ln_eligible(p)) return gemm_x3_wres(p, s);
     }
@@ -206,11 +195,8 @@ static int convt_pair(const DecEngine& e, int F, const float* x, int K0, const f
     // instead of four times and the pixel shuffle is address arithmetic in the epilogue (conv_f16x3.hip, GemmP::shuf_g).
     auto stage = [&](const float* A, long M, int K, const half_t* hl, const float* bias, int nsub, int g, float* C, int a,
                      const float* r) {
-      GemmP p;
-      p.A = A, p.W = hl, p.W_lo = hl + (size_t)4 * nsub * K, p.bias = bias, p.C = C, p.res = r, p.act = a;
-      p.alpha = 1.0f / (float)(1 << F16X3_WSHIFT);
-      p.M = (int)M, p.N = 4 * nsub, p.K = K, p.ldw = K, p.ldc = nsub, p.ldr = nsub;
-      p.conv = 1, p.cH = (int)M, p.cW = 1, p.cC = K, p.KH = 1, p.KW = 1, p.cstride = 1, p.cpad = 0, p.OH = (int)M, p.OW = 1;
+      GemmP p = gemm_linear(A, K, nullptr, bias, C, nsub, (int)M, 4 * nsub, K, a, r, nsub);
+      gemm_split_planes(p, hl);
       p.shuf_g = g, p.shuf_n = nsub;
       return conv_f16x3(p, s);
     };
@@ -218,11 +204,8 @@ static int convt_pair(const DecEngine& e, int F, const float* x, int K0, const f
     // the LayerNorm2d + GELU between the stages runs in the first stage's epilogue, and (dot_hyper) the mask's dot product in the
     // second's — the same arithmetic as the kernels they replace, operation for operation (tests/test_gpu_kernels.py)
     auto fused = [&](const float* A, long M, int K, const half_t* hl, const float* bias, int nsub, int g, float* C, int epi) {
-      GemmP p;
-      p.A = A, p.W = hl, p.W_lo = hl + (size_t)4 * nsub * K, p.bias = bias, p.C = C, p.act = ACT_GELU;
-      p.alpha = 1.0f / (float)(1 << F16X3_WSHIFT);
-      p.M = (int)M, p.N = 4 * nsub, p.K = K, p.ldw = K, p.ldc = epi == 2 ? 1 : nsub, p.ldr = nsub;
-      p.conv = 1, p.cH = (int)M, p.cW = 1, p.cC = K, p.KH = 1, p.KW = 1, p.cstride = 1, p.cpad = 0, p.OH = (int)M, p.OW = 1;
+      GemmP p = gemm_linear(A, K, nullptr, bias, C, epi == 2 ? 1 : nsub, (int)M, 4 * nsub, K, ACT_GELU, nullptr, nsub);
+      gemm_split_planes(p, hl);
       p.shuf_g = g, p.shuf_n = nsub, p.epi = epi;
       if (epi == 1) p.epi_a = lnw, p.epi_b = lnb, p.epi_eps = 1e-6f;
       else p.epi_a = dot_hyper, p.epi_ld = dot_ld;
@@ -256,6 +239,23 @@ static int convt_pair(const DecEngine& e, int F, const float* x, int K0, const f
   q.M = (int)(4 * FP), q.N = N1, q.K = N0, q.lda = N0, q.ldw = N0, q.ldc = N1, q.ldr = N1, q.act = act;
   q.nb1 = 4, q.sW1 = (long)N1 * N0, q.sRowmap1 = 4L * e.max_frames * P;
   return gemm_f32(q, s);
+}
+
+// HQ-SAM's embedding_maskfeature: uh1 = conv3x3(GELU(LN2d(conv3x3(up)))) + hq_feat over F maps of 4g x 4g pixels (uh0: the
+// hidden map).  res_mod > 0: hq_feat is ONE image's block of res_mod rows, broadcast over the maps.
+// (with split-fp16 planes packed: 3-term fp16 MFMAs, fp32-grade at 2.25x the f32 MFMA rate — the two convolutions are 4.8 of an
+//  HQ pass's 8.6 GFLOP)
+static int hq_maskfeature(const DecEngine& e, int F, const float* up, const float* hq_feat, int res_mod, float* uh0, float* uh1,
+                          hipStream_t s) {
+  const int C = e.c.C, Lr = 4 * e.c.grid;
+  const DecEngine::HqW& hq = e.hq;
+  const ConvW mf0{hq.mf0_w, hq.mf0_b, hq.mf0_hl, C / 8, C / 4, 3, 3, 1, 1, 1}, mf1{hq.mf1_w, hq.mf1_b, hq.mf1_hl, C / 4, C / 8, 3, 3, 1, 1, 1};
+  GemmP p = gemm_conv(mf0, up, F, Lr, Lr, uh0);
+  SAMPT_TRY(launch_conv(p, mf0.w_hl, s));
+  SAMPT_TRY(layernorm_rows(uh0, hq.mfln_w, hq.mfln_b, uh0, (long)F * Lr * Lr, C / 4, 1e-6f, nullptr, 0, ACT_GELU, s));
+  GemmP q = gemm_conv(mf1, uh0, F, Lr, Lr, uh1);
+  q.res = hq_feat, q.ldr = C / 8, q.res_mod = res_mod;
+  return launch_conv(q, mf1.w_hl, s);
 }
 
 int DecEngine::hq_features(int F, const float* features, const float* interm, float* out, Arena& ws, hipStream_t s) {
@@ -398,28 +398,7 @@ int DecEngine::decode(int F, const float* features, const float* hq_feat, const 
   } else {
     // HQ-SAM: upscaled_hq = conv3x3(GELU(LN2d(conv3x3(upscaled)))) + hq_features ;  mask = <hyper0, upscaled> +
     // <hf_mlp(hq token), upscaled_hq>   (MaskDecoderHQ.predict_masks, hq_token_only=False)
-    const int Lr = 4 * g;
-    GemmP p;
-    p.A = b.up1, p.W = hq.mf0_w, p.bias = hq.mf0_b, p.C = uh0;
-    p.M = (int)(16 * FP), p.N = C / 4, p.K = 9 * (C / 8), p.ldw = p.K, p.ldc = C / 4;
-    p.conv = 1, p.cH = Lr, p.cW = Lr, p.cC = C / 8, p.KH = 3, p.KW = 3, p.cstride = 1, p.cpad = 1, p.OH = Lr, p.OW = Lr;
-    if (hq.mf0_hl) {   // 3-term split-fp16 MFMAs: fp32-grade, 2.25x the f32 MFMA rate (the two convs are 4.8 of an HQ pass's 8.6 GFLOP)
-      p.W = hq.mf0_hl, p.W_lo = hq.mf0_hl + (size_t)p.N * p.K, p.alpha = 1.0f / (float)(1 << F16X3_WSHIFT);
-      SAMPT_TRY(conv_f16x3(p, s));
-    } else {
-      SAMPT_TRY(gemm_f32(p, s));
-    }
-    SAMPT_TRY(layernorm_rows(uh0, hq.mfln_w, hq.mfln_b, uh0, 16L * FP, C / 4, 1e-6f, nullptr, 0, ACT_GELU, s));
-    GemmP q;
-    q.A = uh0, q.W = hq.mf1_w, q.bias = hq.mf1_b, q.C = uh1, q.res = hq_feat;
-    q.M = (int)(16 * FP), q.N = C / 8, q.K = 9 * (C / 4), q.ldw = q.K, q.ldc = C / 8, q.ldr = C / 8;
-    q.conv = 1, q.cH = Lr, q.cW = Lr, q.cC = C / 4, q.KH = 3, q.KW = 3, q.cstride = 1, q.cpad = 1, q.OH = Lr, q.OW = Lr;
-    if (hq.mf1_hl) {
-      q.W = hq.mf1_hl, q.W_lo = hq.mf1_hl + (size_t)q.N * q.K, q.alpha = 1.0f / (float)(1 << F16X3_WSHIFT);
-      SAMPT_TRY(conv_f16x3(q, s));
-    } else {
-      SAMPT_TRY(gemm_f32(q, s));
-    }
+    SAMPT_TRY(hq_maskfeature(*this, F, b.up1, hq_feat, 0, uh0, uh1, s));
     const float* hq_tok = queries + 5 * C;
     SAMPT_TRY(l.lin(hq_tok, F, C, hq.mlp_w[0], hq.mlp_b[0], b.t0, C, ACT_RELU, nullptr, Nt * C));
     SAMPT_TRY(l.lin(b.t0, F, C, hq.mlp_w[1], hq.mlp_b[1], b.t1, C, ACT_RELU));
@@ -587,29 +566,8 @@ int DecEngine::decode_points(int n, const float* features, const float* hq_feat,
   SAMPT_TRY(mlp3(0, iou_w, iou_b, select ? iou3 : iou_out, ms, ms, multi ? 1 : 0));
   if (!is_hq())
     return sam_mask_dot_multi(b.up1, hyper, ms, ms, nullptr, nullptr, 0, nullptr, low_out, nullptr, F, 16 * P, C8, s);
-  const int Lr = 4 * g;
-  GemmP p;
-  p.A = b.up1, p.W = hq.mf0_w, p.bias = hq.mf0_b, p.C = uh0;
-  p.M = (int)(16 * FP), p.N = C / 4, p.K = 9 * C8, p.ldw = p.K, p.ldc = C / 4;
-  p.conv = 1, p.cH = Lr, p.cW = Lr, p.cC = C8, p.KH = 3, p.KW = 3, p.cstride = 1, p.cpad = 1, p.OH = Lr, p.OW = Lr;
-  if (hq.mf0_hl) {
-    p.W = hq.mf0_hl, p.W_lo = hq.mf0_hl + (size_t)p.N * p.K, p.alpha = 1.0f / (float)(1 << F16X3_WSHIFT);
-    SAMPT_TRY(conv_f16x3(p, s));
-  } else {
-    SAMPT_TRY(gemm_f32(p, s));
-  }
-  SAMPT_TRY(layernorm_rows(uh0, hq.mfln_w, hq.mfln_b, uh0, 16L * FP, C / 4, 1e-6f, nullptr, 0, ACT_GELU, s));
   // + hq_features: ONE image's [16 P][C/8] block, broadcast over the items (res_mod)
-  GemmP q;
-  q.A = uh0, q.W = hq.mf1_w, q.bias = hq.mf1_b, q.C = uh1, q.res = hq_feat, q.res_mod = 16 * P;
-  q.M = (int)(16 * FP), q.N = C8, q.K = 9 * (C / 4), q.ldw = q.K, q.ldc = C8, q.ldr = C8;
-  q.conv = 1, q.cH = Lr, q.cW = Lr, q.cC = C / 4, q.KH = 3, q.KW = 3, q.cstride = 1, q.cpad = 1, q.OH = Lr, q.OW = Lr;
-  if (hq.mf1_hl) {
-    q.W = hq.mf1_hl, q.W_lo = hq.mf1_hl + (size_t)q.N * q.K, q.alpha = 1.0f / (float)(1 << F16X3_WSHIFT);
-    SAMPT_TRY(conv_f16x3(q, s));
-  } else {
-    SAMPT_TRY(gemm_f32(q, s));
-  }
+  SAMPT_TRY(hq_maskfeature(*this, F, b.up1, hq_feat, 16 * P, uh0, uh1, s));
   SAMPT_TRY(mlp3(5, hq.mlp_w, hq.mlp_b, t3, C8, C8, 0));
   return sam_mask_dot_multi(b.up1, hyper, ms, 1, uh1, t3, C8, select ? iou3 : nullptr, low_out, select ? iou_out : nullptr, F,
                             16 * P, C8, s);

@@ -1,37 +1,16 @@
 // PIPS engine: fnet (BasicEncoder, pips.py:191-287) and the iterative point-update window (pips.py:439-620).
 #include <stdlib.h>
 
-#include "engine.h"
+#include "engine_layers.h"
 
 namespace sampt {
-
-static int load_conv(const WeightMap& w, const std::string& name, int cin, int cout, int k, int stride, int pad,
-                     ConvW& c) {
-  c.w = w.f(name + ".weight");
-  c.b = w.f(name + ".bias");
-  c.w_hl = (cin % 32 == 0 && w.has(name + ".weight_hl")) ? w.h(name + ".weight_hl") : nullptr;
-  c.cin = cin, c.cout = cout, c.k = k, c.stride = stride, c.pad = pad;
-  return (c.w && c.b) ? SAMPT_OK : SAMPT_ERR_ARG;
-}
 
 int PipsEngine::init_fnet(const WeightMap& w) {
   int rc = SAMPT_OK;
   // conv weights arrive repacked [Cout][KH*KW*Cin] (ci fastest); the stem's Cin is zero-padded 3 -> 4
   rc |= load_conv(w, "fnet.conv1", 4, 64, 7, 2, 3, stem);
   const int dims[4] = {64, 96, 128, 128}, strides[4] = {1, 2, 2, 2};
-  int in_planes = 64;
-  for (int li = 0; li < 4; ++li) {
-    for (int bi = 0; bi < 2; ++bi) {
-      int cin = bi == 0 ? in_planes : dims[li];
-      int st = bi == 0 ? strides[li] : 1;
-      std::string p = "fnet.layer" + std::to_string(li + 1) + "." + std::to_string(bi);
-      rc |= load_conv(w, p + ".conv1", cin, dims[li], 3, st, 1, blk[li][bi][0]);
-      rc |= load_conv(w, p + ".conv2", dims[li], dims[li], 3, 1, 1, blk[li][bi][1]);
-      has_down[li][bi] = (bi == 0 && st != 1);
-      if (has_down[li][bi]) rc |= load_conv(w, p + ".downsample.0", cin, dims[li], 1, st, 0, blk[li][bi][2]);
-    }
-    in_planes = dims[li];
-  }
+  rc |= load_res_layers(w, "fnet", 4, dims, strides, blk);
   rc |= load_conv(w, "fnet.conv2", 416, 256, 3, 1, 1, conv2);
   rc |= load_conv(w, "fnet.conv3", 256, 128, 1, 1, 0, conv3);
   if (rc != SAMPT_OK || !w.missing.empty()) {
@@ -71,50 +50,6 @@ int PipsEngine::init(const WeightMap& w) {
   return SAMPT_OK;
 }
 
-// conv (implicit GEMM, bias fused) -> raw output; returns output dims
-struct Planes {          // an activation map pre-split into fp16 planes (written by run_inorm), or {null, null}
-  half_t *hi = nullptr, *lo = nullptr;
-};
-
-struct NormCtx {
-  double* partials;
-  float* mean_rstd;
-  int chunks = 0;          // > 0: the convolution that produced the map already wrote its InstanceNorm partial sums (this many per image)
-};
-
-// nc non-null: an InstanceNorm follows — a convolution that can (the halo-tiled 3 x 3 kernel) sums its share of the statistics
-static int run_conv(const ConvW& c, const float* x, int n, int H, int W, float* y, int& OH, int& OW, bool dry,
-                    hipStream_t s, Planes xp = Planes(), NormCtx* nc = nullptr) {
-  OH = (H + 2 * c.pad - c.k) / c.stride + 1;
-  OW = (W + 2 * c.pad - c.k) / c.stride + 1;
-  if (dry) return SAMPT_OK;
-  GemmP p;
-  p.A = x, p.W = c.w, p.bias = c.b, p.C = y;
-  p.M = n * OH * OW, p.N = c.cout, p.K = c.k * c.k * c.cin;
-  p.ldw = p.K, p.ldc = c.cout;
-  p.conv = 1, p.cH = H, p.cW = W, p.cC = c.cin, p.KH = c.k, p.KW = c.k, p.cstride = c.stride, p.cpad = c.pad;
-  p.OH = OH, p.OW = OW;
-  if (c.w_hl) {  // split-fp16 weights packed by the host: fp32-grade result on the fp16 matrix pipe
-    p.W = c.w_hl, p.W_lo = c.w_hl + (size_t)c.cout * p.K;
-    p.alpha = 1.0f / (float)(1 << F16X3_WSHIFT);
-    if (xp.hi) p.A = xp.hi, p.A_lo = xp.lo;     // activations already split by the producing InstanceNorm
-    if (nc && g_conv_halo && (g_conv_in_stats & 1) && conv3x3_halo_eligible(p)) p.in_part = nc->partials, nc->chunks = conv3x3_halo_tiles(p);
-    return conv_f16x3(p, s);
-  }
-  return gemm_f32(p, s);
-}
-
-// InstanceNorm (+ReLU) (+skip add + ReLU), in place on y.  planes_only: the normalised map is only ever read by a split-fp16
-// convolution (through out.hi / out.lo), so its f32 copy is not written (y keeps the raw convolution output)
-static int run_inorm(NormCtx& nc, float* y, int n, long hw, int C, int relu1, const float* skip, bool dry,
-                     hipStream_t s, Planes out = Planes(), bool planes_only = false) {
-  if (dry) return SAMPT_OK;
-  if (nc.chunks > 0) SAMPT_TRY(instnorm_finalize(nc.partials, n, nc.chunks, hw, C, 1e-5f, nc.mean_rstd, s));
-  else SAMPT_TRY(instnorm_stats(y, n, hw, C, 1e-5f, nc.partials, nc.mean_rstd, s));
-  nc.chunks = 0;
-  return instnorm_apply(y, nc.mean_rstd, skip, planes_only && out.hi ? nullptr : y, n, hw, C, relu1, s, out.hi, out.lo);
-}
-
 int PipsEngine::fnet(const uint8_t* frames, int nf, int H, int W, float* const out[4], Arena& ws, hipStream_t s) {
   const bool dry = ws.dry();
   const int H2 = (H + 6 - 7) / 2 + 1, W2 = (W + 6 - 7) / 2 + 1;
@@ -139,16 +74,9 @@ int PipsEngine::fnet(const uint8_t* frames, int nf, int H, int W, float* const o
   float* x0 = ws.f32((size_t)nf * H * W * 4);
   if (!dry) SAMPT_TRY(rgb_u8chw_to_nhwc4(frames, frames_f32, x0, nf, H, W, s));
   int h, w;
-  // Every InstanceNorm output that feeds a split-fp16 convolution is also written as two fp16 planes (same bytes as the
-  // f32 map): the convolution then stages ready-made halves instead of splitting each element once per filter tap.
-  auto planes = [&](size_t elems, const ConvW& consumer) {
-    Planes pl;
-    if (consumer.w_hl) pl.hi = ws.f16(elems), pl.lo = ws.f16(elems);
-    return pl;
-  };
   float* cur = ws.f32((size_t)nf * H2 * W2 * 64);
-  Planes cur_p = planes((size_t)nf * H2 * W2 * 64, blk[0][0][0]);
-  if (blk[0][0][0].w_hl && g_conv_halo && stem.k == 7 && stem.stride == 2 && stem.pad == 3 && stem.cin == 4 && stem.cout == 64) {
+  Planes cur_p = planes_for(ws, (size_t)nf * H2 * W2 * 64, blk[0][0][0]);
+  if (blk[0][0][0].w_hl && g_conv_halo && stem.kh == 7 && stem.kw == 7 && stem.stride == 2 && stem.ph == 3 && stem.pw == 3 && stem.cin == 4 && stem.cout == 64) {
     // split-fp16 mode: the stem as 3-term fp16 products too, one K slab per kernel row (conv_stem_x3.hip), InstanceNorm sums fused
     h = (H + 6 - 7) / 2 + 1, w = (W + 6 - 7) / 2 + 1;
     if (!dry) {
@@ -156,7 +84,7 @@ int PipsEngine::fnet(const uint8_t* frames, int nf, int H, int W, float* const o
       if (g_conv_in_stats & 2) nc.chunks = conv_stem_tiles(H, W);
     }
   } else {
-    SAMPT_TRY(run_conv(stem, x0, nf, H, W, cur, h, w, dry, s));
+    SAMPT_TRY(run_conv(stem, x0, nf, H, W, cur, 64, ACT_NONE, nullptr, h, w, dry, s));
   }
   SAMPT_TRY(run_inorm(nc, cur, nf, (long)h * w, 64, 1, nullptr, dry, s, cur_p));
   const int dims[4] = {64, 96, 128, 128};
@@ -164,37 +92,16 @@ int PipsEngine::fnet(const uint8_t* frames, int nf, int H, int W, float* const o
   int sh[4], sw[4];
   for (int li = 0; li < 4; ++li) {
     for (int bi = 0; bi < 2; ++bi) {
-      const ConvW& c1 = blk[li][bi][0];
-      const ConvW& c2 = blk[li][bi][1];
-      int oh, ow, oh2, ow2;
-      int ohh = (h + 2 - 3) / c1.stride + 1, oww = (w + 2 - 3) / c1.stride + 1;
-      const size_t oel = (size_t)nf * ohh * oww * dims[li];
-      float* y1 = ws.f32(oel);
-      float* y2 = ws.f32(oel);
-      Planes y1_p = planes(oel, c2);
       // the block's output feeds the next block's conv1 (and its 1x1 downsample); the last block's only the resize
-      const bool last = li == 3 && bi == 1;
-      Planes y2_p = last ? Planes() : planes(oel, bi == 0 ? blk[li][1][0] : blk[li + 1][0][0]);
-      SAMPT_TRY(run_conv(c1, cur, nf, h, w, y1, oh, ow, dry, s, cur_p, &nc));
-      SAMPT_TRY(run_inorm(nc, y1, nf, (long)oh * ow, dims[li], 1, nullptr, dry, s, y1_p, true));   // y1 feeds conv2 only
-      SAMPT_TRY(run_conv(c2, y1, nf, oh, ow, y2, oh2, ow2, dry, s, y1_p, &nc2));
-      const float* skip = cur;
-      if (has_down[li][bi]) {
-        float* dn = y1;  // y1 is dead after conv2 has consumed it (stream order)
-        int dh, dw;
-        SAMPT_TRY(run_conv(blk[li][bi][2], cur, nf, h, w, dn, dh, dw, dry, s, cur_p));
-        SAMPT_TRY(run_inorm(nc, dn, nf, (long)dh * dw, dims[li], 0, nullptr, dry, s));
-        skip = dn;
-      }
-      SAMPT_TRY(run_inorm(nc2, y2, nf, (long)oh2 * ow2, dims[li], 1, skip, dry, s, y2_p));
-      cur = y2, cur_p = y2_p, h = oh2, w = ow2;
+      const ConvW* next = bi == 0 ? &blk[li][1][0] : (li < 3 ? &blk[li + 1][0][0] : nullptr);
+      SAMPT_TRY(res_block(blk[li][bi], true, next, cur, cur_p, nf, h, w, nc, nc2, ws, s));
     }
     scale_out[li] = cur, sh[li] = h, sw[li] = w;
   }
   const int H4 = H / stride, W4 = W / stride;
   // the 4 scales resized to H/4 x W/4 and concatenated (pips.py:266-281): written straight as split fp16 planes when the
   // 416 -> 256 convolution takes them (same bytes as the f32 map, which is then never materialised)
-  Planes cat_p = planes((size_t)nf * H4 * W4 * 416, conv2);
+  Planes cat_p = planes_for(ws, (size_t)nf * H4 * W4 * 416, conv2);
   float* cat = cat_p.hi ? nullptr : ws.f32((size_t)nf * H4 * W4 * 416);
   const int coff[4] = {0, 64, 160, 288};
   if (!dry)
@@ -203,10 +110,10 @@ int PipsEngine::fnet(const uint8_t* frames, int nf, int H, int W, float* const o
                                      cat_p.lo));
   float* y = ws.f32((size_t)nf * H4 * W4 * 256);
   int oh, ow;
-  Planes y_p = planes((size_t)nf * H4 * W4 * 256, conv3);
-  SAMPT_TRY(run_conv(conv2, cat, nf, H4, W4, y, oh, ow, dry, s, cat_p, &nc));
+  Planes y_p = planes_for(ws, (size_t)nf * H4 * W4 * 256, conv3);
+  SAMPT_TRY(run_conv(conv2, cat, nf, H4, W4, y, 256, ACT_NONE, nullptr, oh, ow, dry, s, cat_p, &nc));
   SAMPT_TRY(run_inorm(nc, y, nf, (long)oh * ow, 256, 1, nullptr, dry, s, y_p, true));             // feeds the 1 x 1 conv3 only
-  SAMPT_TRY(run_conv(conv3, y, nf, oh, ow, out[0], oh, ow, dry, s, y_p));
+  SAMPT_TRY(run_conv(conv3, y, nf, oh, ow, out[0], 128, ACT_NONE, nullptr, oh, ow, dry, s, y_p));
   if (!dry) {
     int ph = H4, pw = W4;
     for (int l = 1; l < 4; ++l) {
@@ -215,15 +122,6 @@ int PipsEngine::fnet(const uint8_t* frames, int nf, int H, int W, float* const o
     }
   }
   return ws.ok() ? SAMPT_OK : SAMPT_ERR_WORKSPACE;
-}
-
-static int lin(const float* A, int M, int K, int lda, const float* W, const float* b, float* C, int N, int act,
-               const float* res, hipStream_t s, float* skws = nullptr, size_t skn = 0) {
-  GemmP p;
-  p.A = A, p.W = W, p.bias = b, p.C = C, p.res = res;
-  p.splitk_ws = skws, p.splitk_ws_floats = skn;
-  p.M = M, p.N = N, p.K = K, p.lda = lda, p.ldw = K, p.ldc = N, p.ldr = N, p.act = act;
-  return gemm_f32(p, s);
 }
 
 #define PIPS_LAUNCH(expr) do { ++nl; SAMPT_TRY(expr); } while (0)     // every kernel launch of a window is counted where it is made
@@ -260,7 +158,7 @@ int PipsEngine::update(const PyramidLevels& pyr, const int* frame_idx, int n, co
       // the same 30 launches with the channel MLP as split-fp16 products (pips_mixer_x3.hip): [slab sum + residual -> token
       // mixing -> LayerNorm2 -> operand images] and [fc1 -> GELU -> fc2 slabs from the packed weight stream]
       PIPS_LAUNCH(pips_corr_sample(pyr, frame_idx, S, n, 128, ffeats, coords, x, LDX, 128, s, times));
-      PIPS_LAUNCH(lin(x, R, LDX, LDX, in_w, in_b, hbuf, D, ACT_NONE, nullptr, s));
+      PIPS_LAUNCH(run_linear(x, LDX, in_w, in_b, hbuf, D, R, D, LDX, ACT_NONE, nullptr, D, s));
       float* xpp[2] = {hbuf2, lnb};
       const float* prev = hbuf;
       for (int i = 0; i < 12; ++i) {
@@ -275,7 +173,7 @@ int PipsEngine::update(const PyramidLevels& pyr, const int* frame_idx, int n, co
       // 30 launches per iteration: input (1), in-projection (1), per block [sum of the previous block's slabs + residual ->
       // token mixing] and [LayerNorm -> fc1 -> GELU -> fc2 slabs] (2 x 12), last sum + LayerNorm + token mean (1), head, update
       PIPS_LAUNCH(pips_corr_sample(pyr, frame_idx, S, n, 128, ffeats, coords, x, LDX, 128, s, times));
-      PIPS_LAUNCH(lin(x, R, LDX, LDX, in_w, in_b, hbuf, D, ACT_NONE, nullptr, s));
+      PIPS_LAUNCH(run_linear(x, LDX, in_w, in_b, hbuf, D, R, D, LDX, ACT_NONE, nullptr, D, s));
       float* xpp[2] = {hbuf2, lnb};
       const float* prev = hbuf;
       for (int i = 0; i < 12; ++i) {
@@ -289,19 +187,19 @@ int PipsEngine::update(const PyramidLevels& pyr, const int* frame_idx, int n, co
     } else {
       PIPS_LAUNCH(pips_corr_sample(pyr, frame_idx, S, n, 128, ffeats, coords, x, LDX, 128, s));
       PIPS_LAUNCH(pips_build_input(ffeats, coords, times, S, n, x, LDX, s));
-      PIPS_LAUNCH(lin(x, R, LDX, LDX, in_w, in_b, hbuf, D, ACT_NONE, nullptr, s));
+      PIPS_LAUNCH(run_linear(x, LDX, in_w, in_b, hbuf, D, R, D, LDX, ACT_NONE, nullptr, D, s));
       // 12 mixer blocks, 4 launches each: token mixing, LayerNorm, fc1 + GELU, fc2 + residual (thin GEMMs: K split inside
       // the workgroup, no split-K grid + reduction pass).
       for (int i = 0; i < 12; ++i) {
         const MixBlk& m = mix[i];
         PIPS_LAUNCH(pips_token_mix(hbuf, hbuf2, m.ln1w, m.ln1b, m.tw1, m.tb1, m.tw2, m.tb2, n, S, D, s));
         PIPS_LAUNCH(layernorm_rows(hbuf2, m.ln2w, m.ln2b, lnb, R, D, 1e-5f, nullptr, 0, ACT_NONE, s));
-        PIPS_LAUNCH(lin(lnb, R, D, D, m.cw1, m.cb1, hid, 4 * D, ACT_GELU, nullptr, s));
-        PIPS_LAUNCH(lin(hid, R, 4 * D, 4 * D, m.cw2, m.cb2, hbuf, D, ACT_NONE, hbuf2, s));
+        PIPS_LAUNCH(run_linear(lnb, D, m.cw1, m.cb1, hid, 4 * D, R, 4 * D, D, ACT_GELU, nullptr, 4 * D, s));
+        PIPS_LAUNCH(run_linear(hid, 4 * D, m.cw2, m.cb2, hbuf, D, R, D, 4 * D, ACT_NONE, hbuf2, D, s));
       }
       PIPS_LAUNCH(pips_ln_mean(hbuf, oln_w, oln_b, mean, n, S, D, s));
     }
-    PIPS_LAUNCH(lin(mean, n, D, D, head_w, head_b, delta, S * 130, ACT_NONE, nullptr, s));
+    PIPS_LAUNCH(run_linear(mean, D, head_w, head_b, delta, S * 130, n, S * 130, D, ACT_NONE, nullptr, S * 130, s));
     PIPS_LAUNCH(pips_update(delta, gn_w, gn_b, up_wT, up_b, ffeats, coords, coords0, S, n, s));
   }
   PIPS_LAUNCH(pips_finalize(ffeats, vis_w, vis_b, coords, (float)stride, S, n, traj_out, vis_out, s));

@@ -1,7 +1,7 @@
 // PIPS++ engine (row f4): whole-chunk iterative refinement (pips_plus_plus.py:436-546) on top of the PIPS kernels — the
 // feature pyramid, the fused local correlation sampler (three templates per iteration) and the bilinear feature gather
 // are shared; the DeltaBlock (1-D ResNet over time, :263-342) runs as implicit-GEMM convolutions over [n][S][1][C].
-#include "engine.h"
+#include "engine_layers.h"
 
 namespace sampt {
 
@@ -16,14 +16,13 @@ int Pips2Engine::init(const WeightMap& w, int stride_) {
     error = enc.error;
     return rc;
   }
-  auto conv = [&](const std::string& p, int cin, int cout, Conv1& c) {
-    c.w = w.f(p + ".conv.weight"), c.b = w.f(p + ".conv.bias"), c.cin = cin, c.cout = cout;
-  };
-  conv("delta_block.first_block_conv", 720, 128, first);            // 718 input channels zero-padded to 720
+  // Conv1dPad(k = 3, "same") over the S frames of every point, as a 3 x 1 convolution over an [n][S][1][C] image:
+  // y[pt*S+s][co] = b + sum_{d,ci} x[pt*S+s+d-1][ci] W[co][d][ci]
+  load_conv(w, "delta_block.first_block_conv.conv", 720, 128, 3, 1, 1, 1, 0, first);   // 718 input channels zero-padded to 720
   for (int i = 0; i < 8; ++i) {
     const std::string p = "delta_block.basicblock_list." + std::to_string(i);
-    conv(p + ".conv1", kBlocks[i][0], kBlocks[i][1], blk[i][0]);
-    conv(p + ".conv2", kBlocks[i][1], kBlocks[i][1], blk[i][1]);
+    load_conv(w, p + ".conv1.conv", kBlocks[i][0], kBlocks[i][1], 3, 1, 1, 1, 0, blk[i][0]);
+    load_conv(w, p + ".conv2.conv", kBlocks[i][1], kBlocks[i][1], 3, 1, 1, 1, 0, blk[i][1]);
   }
   dense_w = w.f("delta_block.dense.weight"), dense_b = w.f("delta_block.dense.bias");
   omega = w.f("__omega");
@@ -32,17 +31,6 @@ int Pips2Engine::init(const WeightMap& w, int stride_) {
     return SAMPT_ERR_ARG;
   }
   return SAMPT_OK;
-}
-
-// Conv1dPad(k = 3, "same") over the S frames of every point: y[pt*S+s][co] = b + sum_{d,ci} x[pt*S+s+d-1][ci] W[co][d][ci]
-static int conv1d(const Pips2Engine::Conv1& c, const float* x, int n, int S, float* y, int act, const float* res,
-                  hipStream_t s) {
-  GemmP p;
-  p.A = x, p.W = c.w, p.bias = c.b, p.C = y, p.res = res;
-  p.M = n * S, p.N = c.cout, p.K = 3 * c.cin, p.ldw = p.K, p.ldc = c.cout, p.ldr = c.cout, p.act = act;
-  p.conv = 1, p.cH = S, p.cW = 1, p.cC = c.cin, p.KH = 3, p.KW = 1, p.cstride = 1, p.cpad = 1, p.cpadw = 0;
-  p.OH = S, p.OW = 1;
-  return gemm_f32(p, s);
 }
 
 int Pips2Engine::update(const PyramidLevels& pyr, const int* frame_idx, int n, int S, const float* trajs0, int have_init,
@@ -59,6 +47,7 @@ int Pips2Engine::update(const PyramidLevels& pyr, const int* frame_idx, int n, i
   if (!ws.ok()) return SAMPT_ERR_WORKSPACE;
   if (ws.dry()) return SAMPT_OK;
   const int H = pyr.H[0], W = pyr.W[0];
+  int oh, ow;
   SAMPT_TRY(pips2_init(trajs0, pyr.base[0], H, W, frame_idx, (float)stride, S, n, have_init, coords, bak, feats[0], feats[1],
                        feats[2], s));
   for (int it = 0; it < iters; ++it) {
@@ -67,7 +56,7 @@ int Pips2Engine::update(const PyramidLevels& pyr, const int* frame_idx, int n, i
     SAMPT_TRY(pips2_build_input(coords, omega, S, n, x, LDX, s));
     // ---- DeltaBlock: h = relu(conv(x)); 8 residual blocks; relu; dense
     float *h = buf[0], *a = buf[1], *b = buf[2], *c = buf[3];
-    SAMPT_TRY(conv1d(first, x, n, S, h, ACT_RELU, nullptr, s));
+    SAMPT_TRY(run_conv(first, x, n, S, 1, h, 0, ACT_RELU, nullptr, oh, ow, false, s));
     for (int i = 0; i < 8; ++i) {
       const int cin = kBlocks[i][0], cout = kBlocks[i][1];
       const float* in1 = h;
@@ -75,18 +64,15 @@ int Pips2Engine::update(const PyramidLevels& pyr, const int* frame_idx, int n, i
         SAMPT_TRY(instnorm1d_relu(h, a, n, S, cin, s));
         in1 = a;
       }
-      SAMPT_TRY(conv1d(blk[i][0], in1, n, S, b, ACT_NONE, nullptr, s));
+      SAMPT_TRY(run_conv(blk[i][0], in1, n, S, 1, b, 0, ACT_NONE, nullptr, oh, ow, false, s));
       SAMPT_TRY(instnorm1d_relu(b, b, n, S, cout, s));
       const bool fused_skip = cin == cout && i < 7;  // same width: the skip is the GEMM's residual operand
-      SAMPT_TRY(conv1d(blk[i][1], b, n, S, c, ACT_NONE, fused_skip ? h : nullptr, s));
+      SAMPT_TRY(run_conv(blk[i][1], b, n, S, 1, c, 0, ACT_NONE, fused_skip ? h : nullptr, oh, ow, false, s));
       if (!fused_skip) SAMPT_TRY(add_chanpad(c, h, (long)R, cin, cout, i == 7 ? 1 : 0, s));   // last block: + final_relu
       float* t = h;
       h = c, c = t;
     }
-    GemmP d;
-    d.A = h, d.W = dense_w, d.bias = dense_b, d.C = delta;
-    d.M = (int)R, d.N = 2, d.K = 1024, d.lda = 1024, d.ldw = 1024, d.ldc = 2;
-    SAMPT_TRY(gemm_f32(d, s));
+    SAMPT_TRY(run_linear(h, 1024, dense_w, dense_b, delta, 2, (int)R, 2, 1024, ACT_NONE, nullptr, 0, s));
     SAMPT_TRY(pips2_apply_delta(delta, bak, (float)stride, S, n, it == iters - 1, coords, trajs_out, s));
   }
   return SAMPT_OK;

@@ -3,83 +3,39 @@
 // loop over `iters` with no host round trip.  Mask head and convex upsampling run after the last iteration only.
 #include <algorithm>
 
-#include "engine.h"
+#include "engine_layers.h"
 
 namespace sampt {
-
-static int load(const WeightMap& w, const std::string& name, int cin, int cout, int kh, int kw, int stride, int ph, int pw,
-                RaftConv& c) {
-  c.w = w.f(name + ".weight");
-  c.b = w.f(name + ".bias");
-  c.cin = cin, c.cout = cout, c.kh = kh, c.kw = kw, c.stride = stride, c.ph = ph, c.pw = pw;
-  return (c.w && c.b) ? SAMPT_OK : SAMPT_ERR_ARG;
-}
 
 static const int kDims[3] = {64, 96, 128}, kStrides[3] = {1, 2, 2};
 
 static int load_encoder(const WeightMap& w, const std::string& pre, RaftEngine::Enc& e) {
-  int rc = load(w, pre + ".conv1", 4, 64, 7, 7, 2, 3, 3, e.stem);      // Cin zero-padded 3 -> 4
-  int in_planes = 64;
-  for (int li = 0; li < 3; ++li) {
-    for (int bi = 0; bi < 2; ++bi) {
-      const int cin = bi == 0 ? in_planes : kDims[li], st = bi == 0 ? kStrides[li] : 1;
-      const std::string p = pre + ".layer" + std::to_string(li + 1) + "." + std::to_string(bi);
-      rc |= load(w, p + ".conv1", cin, kDims[li], 3, 3, st, 1, 1, e.blk[li][bi][0]);
-      rc |= load(w, p + ".conv2", kDims[li], kDims[li], 3, 3, 1, 1, 1, e.blk[li][bi][1]);
-      if (st != 1) rc |= load(w, p + ".downsample.0", cin, kDims[li], 1, 1, st, 0, 0, e.blk[li][bi][2]);
-    }
-    in_planes = kDims[li];
-  }
-  rc |= load(w, pre + ".conv2", 128, 256, 1, 1, 1, 0, 0, e.out);
-  return rc;
+  int rc = load_conv(w, pre + ".conv1", 4, 64, 7, 2, 3, e.stem);      // Cin zero-padded 3 -> 4
+  rc |= load_res_layers(w, pre, 3, kDims, kStrides, e.blk);
+  return rc | load_conv(w, pre + ".conv2", 128, 256, 1, 1, 0, e.out);
 }
 
 int RaftEngine::init(const WeightMap& w) {
   int rc = load_encoder(w, "fnet", fnet) | load_encoder(w, "cnet", cnet);
   const std::string u = "update_block.";
-  rc |= load(w, u + "encoder.convc1", 352, 256, 1, 1, 1, 0, 0, convc1);     // 324 lookup channels zero-padded to 352
-  rc |= load(w, u + "encoder.convc2", 256, 192, 3, 3, 1, 1, 1, convc2);
-  rc |= load(w, u + "encoder.convf2", 128, 64, 3, 3, 1, 1, 1, convf2);
-  rc |= load(w, u + "encoder.conv", 256, 126, 3, 3, 1, 1, 1, conv);
+  rc |= load_conv(w, u + "encoder.convc1", 352, 256, 1, 1, 1, 0, 0, convc1);     // 324 lookup channels zero-padded to 352
+  rc |= load_conv(w, u + "encoder.convc2", 256, 192, 3, 3, 1, 1, 1, convc2);
+  rc |= load_conv(w, u + "encoder.convf2", 128, 64, 3, 3, 1, 1, 1, convf2);
+  rc |= load_conv(w, u + "encoder.conv", 256, 126, 3, 3, 1, 1, 1, conv);
   convf1_w = w.f(u + "encoder.convf1.weight"), convf1_b = w.f(u + "encoder.convf1.bias");
-  rc |= load(w, u + "gru.convzr1", 384, 256, 1, 5, 1, 0, 2, zr[0]);        // z and r share their input: one N = 256 convolution
-  rc |= load(w, u + "gru.convq1", 384, 128, 1, 5, 1, 0, 2, q[0]);
-  rc |= load(w, u + "gru.convzr2", 384, 256, 5, 1, 1, 2, 0, zr[1]);
-  rc |= load(w, u + "gru.convq2", 384, 128, 5, 1, 1, 2, 0, q[1]);
-  rc |= load(w, u + "flow_head.conv1", 128, 256, 3, 3, 1, 1, 1, fh1);
-  rc |= load(w, u + "flow_head.conv2", 256, 4, 3, 3, 1, 1, 1, fh2);        // N = 2 zero-padded to 4
-  rc |= load(w, u + "mask.0", 128, 256, 3, 3, 1, 1, 1, mask0);
-  rc |= load(w, u + "mask.2", 256, 576, 1, 1, 1, 0, 0, mask2);
+  rc |= load_conv(w, u + "gru.convzr1", 384, 256, 1, 5, 1, 0, 2, zr[0]);        // z and r share their input: one N = 256 convolution
+  rc |= load_conv(w, u + "gru.convq1", 384, 128, 1, 5, 1, 0, 2, q[0]);
+  rc |= load_conv(w, u + "gru.convzr2", 384, 256, 5, 1, 1, 2, 0, zr[1]);
+  rc |= load_conv(w, u + "gru.convq2", 384, 128, 5, 1, 1, 2, 0, q[1]);
+  rc |= load_conv(w, u + "flow_head.conv1", 128, 256, 3, 3, 1, 1, 1, fh1);
+  rc |= load_conv(w, u + "flow_head.conv2", 256, 4, 3, 3, 1, 1, 1, fh2);        // N = 2 zero-padded to 4
+  rc |= load_conv(w, u + "mask.0", 128, 256, 3, 3, 1, 1, 1, mask0);
+  rc |= load_conv(w, u + "mask.2", 256, 576, 1, 1, 1, 0, 0, mask2);
   if (rc != SAMPT_OK || !convf1_w || !convf1_b || !w.missing.empty()) {
     error = "RaftEngine: missing weights: " + w.missing;
     return SAMPT_ERR_ARG;
   }
   return SAMPT_OK;
-}
-
-// y[.., 0:cout] (row stride ldc) = act(conv(x) + bias) on the exact-f32 implicit GEMM
-static int rconv(const RaftConv& c, const float* x, int n, int H, int W, float* y, int ldc, int act, int& OH, int& OW, bool dry,
-                 hipStream_t s) {
-  OH = (H + 2 * c.ph - c.kh) / c.stride + 1;
-  OW = (W + 2 * c.pw - c.kw) / c.stride + 1;
-  if (dry) return SAMPT_OK;
-  GemmP p;
-  p.A = x, p.W = c.w, p.bias = c.b, p.C = y;
-  p.M = n * OH * OW, p.N = c.cout, p.K = c.kh * c.kw * c.cin;
-  p.ldw = p.K, p.ldc = ldc, p.act = act;
-  p.conv = 1, p.cH = H, p.cW = W, p.cC = c.cin, p.KH = c.kh, p.KW = c.kw, p.cstride = c.stride, p.cpad = c.ph, p.cpadw = c.pw;
-  p.OH = OH, p.OW = OW;
-  return gemm_f32(p, s);
-}
-
-struct RaftNorm {
-  double* partials;
-  float* mean_rstd;
-};
-
-static int inorm(const RaftNorm& nc, float* y, int n, long hw, int C, int relu1, const float* skip, hipStream_t s) {
-  SAMPT_TRY(instnorm_stats(y, n, hw, C, 1e-5f, nc.partials, nc.mean_rstd, s));
-  return instnorm_apply(y, nc.mean_rstd, skip, y, n, hw, C, relu1, s);
 }
 
 // BasicEncoder over nf prepared frames x0 [nf][Hp][Wp][4] -> out [nf][Hp/8 * Wp/8][256].  instance: InstanceNorm after every
@@ -88,41 +44,19 @@ static int encode(const RaftEngine::Enc& e, bool instance, const float* x0, int 
                   hipStream_t s) {
   const bool dry = ws.dry();
   const int H2 = Hp / 2, W2 = Wp / 2;
-  RaftNorm nc = {nullptr, nullptr};
+  NormCtx nc = {nullptr, nullptr};
   if (instance) {
     nc.partials = (double*)ws.get(instnorm_partial_doubles(nf, (long)H2 * W2, 256) * sizeof(double));
     nc.mean_rstd = ws.f32((size_t)nf * 256 * 2);
   }
-  const int act = instance ? ACT_NONE : ACT_RELU;
   int h, w;
   float* cur = ws.f32((size_t)nf * H2 * W2 * 64);
-  SAMPT_TRY(rconv(e.stem, x0, nf, Hp, Wp, cur, 64, act, h, w, dry, s));
-  if (instance && !dry) SAMPT_TRY(inorm(nc, cur, nf, (long)h * w, 64, 1, nullptr, s));
+  Planes cur_p;
+  SAMPT_TRY(run_conv(e.stem, x0, nf, Hp, Wp, cur, 64, instance ? ACT_NONE : ACT_RELU, nullptr, h, w, dry, s));
+  if (instance) SAMPT_TRY(run_inorm(nc, cur, nf, (long)h * w, 64, 1, nullptr, dry, s));
   for (int li = 0; li < 3; ++li)
-    for (int bi = 0; bi < 2; ++bi) {
-      const RaftConv &c1 = e.blk[li][bi][0], &c2 = e.blk[li][bi][1], &dn = e.blk[li][bi][2];
-      const int C = kDims[li];
-      int oh = (h + 2 - 3) / c1.stride + 1, ow = (w + 2 - 3) / c1.stride + 1, t0, t1;
-      const size_t oel = (size_t)nf * oh * ow * C;
-      float *y1 = ws.f32(oel), *y2 = ws.f32(oel);
-      SAMPT_TRY(rconv(c1, cur, nf, h, w, y1, C, act, t0, t1, dry, s));
-      if (instance && !dry) SAMPT_TRY(inorm(nc, y1, nf, (long)oh * ow, C, 1, nullptr, s));
-      SAMPT_TRY(rconv(c2, y1, nf, oh, ow, y2, C, act, t0, t1, dry, s));
-      const float* skip = cur;
-      if (c1.stride != 1) {
-        float* d = ws.f32(oel);
-        SAMPT_TRY(rconv(dn, cur, nf, h, w, d, C, ACT_NONE, t0, t1, dry, s));
-        if (instance && !dry) SAMPT_TRY(inorm(nc, d, nf, (long)oh * ow, C, 0, nullptr, s));
-        skip = d;
-      }
-      if (!dry) {
-        if (instance) SAMPT_TRY(inorm(nc, y2, nf, (long)oh * ow, C, 1, skip, s));   // relu(skip + relu(norm(y2)))
-        else SAMPT_TRY(raft_add_relu(y2, skip, y2, (long)oel, s));
-      }
-      cur = y2, h = oh, w = ow;
-    }
-  int t0, t1;
-  return rconv(e.out, cur, nf, h, w, out, 256, ACT_NONE, t0, t1, dry, s);
+    for (int bi = 0; bi < 2; ++bi) SAMPT_TRY(res_block(e.blk[li][bi], instance, nullptr, cur, cur_p, nf, h, w, nc, nc, ws, s));
+  return run_conv(e.out, cur, nf, h, w, out, 256, ACT_NONE, nullptr, h, w, dry, s);
 }
 
 int raft_corr_levels(const float* fmap1, long s1, const float* const pooled[4], const long s2[4], int n, int h8, int w8,
@@ -222,23 +156,23 @@ int RaftEngine::flows(const uint8_t* frames, int T, int H, int W, int iters, flo
     int a, b;
     for (int it = 0; it < iters; ++it) {
       SAMPT_TRY(raft_lookup(lv, coords1, M, look, s));
-      SAMPT_TRY(rconv(convc1, look, P, h8, w8, cor1, 256, ACT_RELU, a, b, false, s));
-      SAMPT_TRY(rconv(convc2, cor1, P, h8, w8, corflo, 256, ACT_RELU, a, b, false, s));              // channels [0, 192)
+      SAMPT_TRY(run_conv(convc1, look, P, h8, w8, cor1, 256, ACT_RELU, nullptr, a, b, false, s));
+      SAMPT_TRY(run_conv(convc2, cor1, P, h8, w8, corflo, 256, ACT_RELU, nullptr, a, b, false, s));              // channels [0, 192)
       SAMPT_TRY(raft_convf1(flow, convf1_w, convf1_b, flo1, P, h8, w8, s));
-      SAMPT_TRY(rconv(convf2, flo1, P, h8, w8, corflo + 192, 256, ACT_RELU, a, b, false, s));        // channels [192, 256)
-      SAMPT_TRY(rconv(conv, corflo, P, h8, w8, hx + 256, 384, ACT_RELU, a, b, false, s));            // hx channels [256, 382)
+      SAMPT_TRY(run_conv(convf2, flo1, P, h8, w8, corflo + 192, 256, ACT_RELU, nullptr, a, b, false, s));        // channels [192, 256)
+      SAMPT_TRY(run_conv(conv, corflo, P, h8, w8, hx + 256, 384, ACT_RELU, nullptr, a, b, false, s));            // hx channels [256, 382)
       for (int pass = 0; pass < 2; ++pass) {                                                       // 1 x 5, then 5 x 1
-        SAMPT_TRY(rconv(zr[pass], hx, P, h8, w8, zrb, 256, ACT_NONE, a, b, false, s));
+        SAMPT_TRY(run_conv(zr[pass], hx, P, h8, w8, zrb, 256, ACT_NONE, nullptr, a, b, false, s));
         SAMPT_TRY(raft_gru_a(zrb, hx, zb, rhx, M, s));
-        SAMPT_TRY(rconv(q[pass], rhx, P, h8, w8, qb, 128, ACT_NONE, a, b, false, s));
+        SAMPT_TRY(run_conv(q[pass], rhx, P, h8, w8, qb, 128, ACT_NONE, nullptr, a, b, false, s));
         SAMPT_TRY(raft_gru_b(qb, zb, hx, hnet, M, s));
       }
-      SAMPT_TRY(rconv(fh1, hnet, P, h8, w8, wide, 256, ACT_RELU, a, b, false, s));
-      SAMPT_TRY(rconv(fh2, wide, P, h8, w8, delta, 4, ACT_NONE, a, b, false, s));
+      SAMPT_TRY(run_conv(fh1, hnet, P, h8, w8, wide, 256, ACT_RELU, nullptr, a, b, false, s));
+      SAMPT_TRY(run_conv(fh2, wide, P, h8, w8, delta, 4, ACT_NONE, nullptr, a, b, false, s));
       SAMPT_TRY(raft_flow_update(delta, coords1, flow, hx, h8, w8, M, s));
     }
-    SAMPT_TRY(rconv(mask0, hnet, P, h8, w8, wide, 256, ACT_RELU, a, b, false, s));
-    SAMPT_TRY(rconv(mask2, wide, P, h8, w8, mask, 576, ACT_NONE, a, b, false, s));
+    SAMPT_TRY(run_conv(mask0, hnet, P, h8, w8, wide, 256, ACT_RELU, nullptr, a, b, false, s));
+    SAMPT_TRY(run_conv(mask2, wide, P, h8, w8, mask, 576, ACT_NONE, nullptr, a, b, false, s));
     SAMPT_TRY(raft_upsample(flow, mask, 0.25f, h8, w8, H, W, p0, n, fwd, bwd, s));
     if (flow_low) SAMPT_TRY(raft_flow_low(flow, flow_low, p0, n, npairs, h8, w8, s));
   }

@@ -8,61 +8,37 @@
 // concatenation in front of the layer's MLP (superglue.py:123) is never made.
 #include <algorithm>
 
-#include "engine.h"
+#include "engine_layers.h"
 
 namespace sampt {
-
-static int sg_conv(const WeightMap& w, const std::string& name, int cin, int cout, int k, RaftConv& c) {
-  c.w = w.f(name + ".weight");
-  c.b = w.f(name + ".bias");
-  c.cin = cin, c.cout = cout, c.kh = k, c.kw = k, c.stride = 1, c.ph = k / 2, c.pw = k / 2;
-  return (c.w && c.b) ? SAMPT_OK : SAMPT_ERR_ARG;
-}
-
-static int sg_linear(const WeightMap& w, const std::string& name, int n, int k, SgLinear& l) {
-  l.w = w.f(name + ".weight");
-  l.b = w.f(name + ".bias");
-  l.n = n, l.k = k;
-  return (l.w && l.b) ? SAMPT_OK : SAMPT_ERR_ARG;
-}
 
 int SgEngine::init(const WeightMap& w) {
   static const char* names[8] = {"conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b"};
   static const int cin[8] = {4, 64, 64, 64, 64, 128, 128, 128}, cout[8] = {64, 64, 64, 64, 128, 128, 128, 128};   // conv1a: 1 -> 4
   int rc = SAMPT_OK;
   const std::string sp_ = "superpoint.", sg_ = "superglue.";
-  for (int i = 0; i < 8; ++i) rc |= sg_conv(w, sp_ + names[i], cin[i], cout[i], 3, sp[i]);
-  rc |= sg_conv(w, sp_ + "convPa", 128, 256, 3, convPa);
-  rc |= sg_conv(w, sp_ + "convPb", 256, 68, 1, convPb);
-  rc |= sg_conv(w, sp_ + "convDa", 128, 256, 3, convDa);
-  rc |= sg_conv(w, sp_ + "convDb", 256, 256, 1, convDb);
+  for (int i = 0; i < 8; ++i) rc |= load_conv(w, sp_ + names[i], cin[i], cout[i], 3, 1, 1, sp[i]);
+  rc |= load_conv(w, sp_ + "convPa", 128, 256, 3, 1, 1, convPa);
+  rc |= load_conv(w, sp_ + "convPb", 256, 68, 1, 1, 0, convPb);
+  rc |= load_conv(w, sp_ + "convDa", 128, 256, 3, 1, 1, convDa);
+  rc |= load_conv(w, sp_ + "convDb", 256, 256, 1, 1, 0, convDb);
   static const int kd[6] = {4, 32, 64, 128, 256, 256};
-  for (int i = 0; i < 5; ++i) rc |= sg_linear(w, sg_ + "kenc." + std::to_string(i), kd[i + 1], kd[i], kenc[i]);
+  for (int i = 0; i < 5; ++i) rc |= load_linear(w, sg_ + "kenc." + std::to_string(i), kd[i + 1], kd[i], kenc[i]);
   for (int l = 0; l < 18; ++l) {
     const std::string p = sg_ + "gnn." + std::to_string(l);
-    rc |= sg_linear(w, p + ".qkv", 768, 256, gnn[l].qkv);
-    rc |= sg_linear(w, p + ".merge", 256, 256, gnn[l].merge);
-    rc |= sg_linear(w, p + ".mlp0", 512, 512, gnn[l].mlp0);
-    rc |= sg_linear(w, p + ".mlp1", 256, 512, gnn[l].mlp1);
+    rc |= load_linear(w, p + ".qkv", 768, 256, gnn[l].qkv);
+    rc |= load_linear(w, p + ".merge", 256, 256, gnn[l].merge);
+    rc |= load_linear(w, p + ".mlp0", 512, 512, gnn[l].mlp0);
+    rc |= load_linear(w, p + ".mlp1", 256, 512, gnn[l].mlp1);
     cross[l] = l & 1;                                     // ['self', 'cross'] * 9
   }
-  rc |= sg_linear(w, sg_ + "final_proj", 256, 256, final_proj);
+  rc |= load_linear(w, sg_ + "final_proj", 256, 256, final_proj);
   bin_score = w.f(sg_ + "bin_score");
   if (rc != SAMPT_OK || !bin_score || !w.missing.empty()) {
     error = "SgEngine: missing weights: " + w.missing;
     return SAMPT_ERR_ARG;
   }
   return SAMPT_OK;
-}
-
-static int conv_relu(const RaftConv& c, const float* x, int H, int W, float* y, int act, hipStream_t s) {
-  GemmP p;
-  p.A = x, p.W = c.w, p.bias = c.b, p.C = y;
-  p.M = H * W, p.N = c.cout, p.K = c.kh * c.kw * c.cin;
-  p.ldw = p.K, p.ldc = c.cout, p.act = act;
-  p.conv = 1, p.cH = H, p.cW = W, p.cC = c.cin, p.KH = c.kh, p.KW = c.kw, p.cstride = 1, p.cpad = c.ph, p.cpadw = c.pw;
-  p.OH = H, p.OW = W;
-  return gemm_f32(p, s);
 }
 
 int SgEngine::detect(const uint8_t* frames, int T, int H, int W, const SgDetectCfg& c, float* kpts, float* kscores, float* desc,
@@ -82,13 +58,13 @@ int SgEngine::detect(const uint8_t* frames, int T, int H, int W, const SgDetectC
   if (dry) return SAMPT_OK;
   for (int f = 0; f < T; ++f) {
     SAMPT_TRY(sg_grey(frames + (size_t)f * 3 * H * W, 1, H, W, x0, s));
-    int h = H, w = W;
+    int h = H, w = W, oh, ow;
     const float* cur = x0;
     float* bufs[2] = {A, B};
     int nb = 0;
     for (int i = 0; i < 8; ++i) {
       float* y = bufs[nb];
-      SAMPT_TRY(conv_relu(sp[i], cur, h, w, y, ACT_RELU, s));
+      SAMPT_TRY(run_conv(sp[i], cur, 1, h, w, y, 0, ACT_RELU, nullptr, oh, ow, false, s));
       cur = y, nb ^= 1;
       if ((i & 1) && i < 7) {                             // pool after conv1b, conv2b, conv3b
         float* q = bufs[nb];
@@ -97,11 +73,11 @@ int SgEngine::detect(const uint8_t* frames, int T, int H, int W, const SgDetectC
       }
     }
     float* head = bufs[nb];                               // the other buffer: cur stays alive for both heads
-    SAMPT_TRY(conv_relu(convPa, cur, h8, w8, head, ACT_RELU, s));
-    SAMPT_TRY(conv_relu(convPb, head, h8, w8, logits, ACT_NONE, s));
+    SAMPT_TRY(run_conv(convPa, cur, 1, h8, w8, head, 0, ACT_RELU, nullptr, oh, ow, false, s));
+    SAMPT_TRY(run_conv(convPb, head, 1, h8, w8, logits, 0, ACT_NONE, nullptr, oh, ow, false, s));
     SAMPT_TRY(sg_scores(logits, 68, 1, h8, w8, dense + (size_t)f * Hs * Ws, s));
-    SAMPT_TRY(conv_relu(convDa, cur, h8, w8, head, ACT_RELU, s));
-    SAMPT_TRY(conv_relu(convDb, head, h8, w8, dmap + (size_t)f * cells * 256, ACT_NONE, s));
+    SAMPT_TRY(run_conv(convDa, cur, 1, h8, w8, head, 0, ACT_RELU, nullptr, oh, ow, false, s));
+    SAMPT_TRY(run_conv(convDb, head, 1, h8, w8, dmap + (size_t)f * cells * 256, 0, ACT_NONE, nullptr, oh, ow, false, s));
   }
   SAMPT_TRY(sg_nms_compact(dense, T, Hs, Ws, c.nms_radius, c.threshold, c.border, c.cap, kpts, kscores, counts_dev, nms_ws, nms_bytes, s));
   if (hipMemcpyAsync(counts_host, counts_dev, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
@@ -111,15 +87,6 @@ int SgEngine::detect(const uint8_t* frames, int T, int H, int W, const SgDetectC
   for (int f = 0; f < T; ++f) most = std::max(most, counts_host[f]);
   if (most > c.cap) return SAMPT_ERR_CAPACITY;            // never truncated silently: nothing beyond cap was written, nothing is sampled
   return sg_sample_descriptors(dmap, T, h8, w8, kpts, counts_dev, c.cap, most, desc, s);
-}
-
-static int linear(const SgLinear& l, const float* a, int lda, float* c, int ldc, int M, int act, const float* res, int ldr,
-                  hipStream_t s) {
-  GemmP p;
-  p.A = a, p.W = l.w, p.bias = l.b, p.C = c, p.res = res;
-  p.M = M, p.N = l.n, p.K = l.k;
-  p.lda = lda, p.ldw = l.k, p.ldc = ldc, p.ldr = ldr, p.act = act;
-  return gemm_f32(p, s);
 }
 
 int SgEngine::match(const float* kp0, const float* sc0, const float* d0, int n0, const float* kp1, const float* sc1, const float* d1,
@@ -148,31 +115,30 @@ int SgEngine::match(const float* kp0, const float* sc0, const float* d0, int n0,
   SAMPT_TRY(sg_kenc_input(kp1, sc1, n1, H, W, kin + (size_t)n0 * 4, s));
   const float* cur = kin;
   for (int i = 0; i < 4; ++i) {
-    SAMPT_TRY(linear(kenc[i], cur, kenc[i].k, t[i & 1], kenc[i].n, N, ACT_RELU, nullptr, 0, s));
+    SAMPT_TRY(run_linear(kenc[i], cur, kenc[i].k, t[i & 1], kenc[i].n, N, ACT_RELU, nullptr, 0, s));
     cur = t[i & 1];
   }
-  SAMPT_TRY(linear(kenc[4], cur, 256, X[0], 512, n0, ACT_NONE, d0, 256, s));
-  SAMPT_TRY(linear(kenc[4], cur + (size_t)n0 * 256, 256, X[0] + (size_t)n0 * 512, 512, n1, ACT_NONE, d1, 256, s));
+  SAMPT_TRY(run_linear(kenc[4], cur, 256, X[0], 512, n0, ACT_NONE, d0, 256, s));
+  SAMPT_TRY(run_linear(kenc[4], cur + (size_t)n0 * 256, 256, X[0] + (size_t)n0 * 512, 512, n1, ACT_NONE, d1, 256, s));
   for (int l = 0; l < 18; ++l) {
     float *x = X[l & 1], *y = X[(l + 1) & 1];
-    SAMPT_TRY(linear(gnn[l].qkv, x, 512, qkv, 768, N, ACT_NONE, nullptr, 0, s));
+    SAMPT_TRY(run_linear(gnn[l].qkv, x, 512, qkv, 768, N, ACT_NONE, nullptr, 0, s));
     const float* src0 = qkv + (cross[l] ? (size_t)n0 * 768 : 0);       // keys of set 0: its own rows, or set 1's
     const float* src1 = qkv + (cross[l] ? 0 : (size_t)n0 * 768);
     const int m0 = cross[l] ? n1 : n0, m1 = cross[l] ? n0 : n1;
     SAMPT_TRY(sg_attention(qkv, 768, src0 + 256, src0 + 512, 768, ao, 256, n0, m0, 4, s));
     SAMPT_TRY(sg_attention(qkv + (size_t)n0 * 768, 768, src1 + 256, src1 + 512, 768, ao + (size_t)n0 * 256, 256, n1, m1, 4, s));
-    SAMPT_TRY(linear(gnn[l].merge, ao, 256, x + 256, 512, N, ACT_NONE, nullptr, 0, s));
-    SAMPT_TRY(linear(gnn[l].mlp0, x, 512, hid, 512, N, ACT_RELU, nullptr, 0, s));
-    SAMPT_TRY(linear(gnn[l].mlp1, hid, 512, y, 512, N, ACT_NONE, x, 512, s));
+    SAMPT_TRY(run_linear(gnn[l].merge, ao, 256, x + 256, 512, N, ACT_NONE, nullptr, 0, s));
+    SAMPT_TRY(run_linear(gnn[l].mlp0, x, 512, hid, 512, N, ACT_RELU, nullptr, 0, s));
+    SAMPT_TRY(run_linear(gnn[l].mlp1, hid, 512, y, 512, N, ACT_NONE, x, 512, s));
   }
   float* fin = X[0];                                       // 18 layers: back in the first buffer
   if (gnn_out && hipMemcpy2DAsync(gnn_out, 1024, fin, 2048, 1024, N, hipMemcpyDeviceToDevice, s) != hipSuccess) return SAMPT_ERR_HIP;
   float* md = t[0];
-  SAMPT_TRY(linear(final_proj, fin, 512, md, 256, N, ACT_NONE, nullptr, 0, s));
+  SAMPT_TRY(run_linear(final_proj, fin, 512, md, 256, N, ACT_NONE, nullptr, 0, s));
   {
-    GemmP p;                                               // scores = mdesc0 mdesc1^T / sqrt(256)
-    p.A = md, p.W = md + (size_t)n0 * 256, p.C = S;
-    p.M = n0, p.N = n1, p.K = 256, p.lda = 256, p.ldw = 256, p.ldc = ldS, p.alpha = 1.0f / 16.0f;
+    GemmP p = gemm_linear(md, 256, md + (size_t)n0 * 256, nullptr, S, ldS, n0, n1, 256);    // scores = mdesc0 mdesc1^T / sqrt(256)
+    p.alpha = 1.0f / 16.0f;
     SAMPT_TRY(gemm_f32(p, s));
   }
   if (scores_out && hipMemcpy2DAsync(scores_out, (size_t)n1 * 4, S, (size_t)ldS * 4, (size_t)n1 * 4, n0, hipMemcpyDeviceToDevice, s) != hipSuccess)

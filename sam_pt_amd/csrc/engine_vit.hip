@@ -8,7 +8,7 @@
 //                          the qkv / fc1 GEMM epilogues and the attention kernel emit them, the next GEMM consumes them.
 // Activations are token-major [rows][channels] throughout (NHWC): the neck's output is directly the decoder's
 // image-token matrix.
-#include "engine.h"
+#include "engine_layers.h"
 
 namespace sampt {
 
@@ -81,21 +81,17 @@ struct G {
   int run(const void* A, int M, int K, const void* W, const float* bias, void* C, int N, int act, int out,
           const float* res, int ldr, const int* rowmap, int res_mod, const int* a_rowmap = nullptr,
           bool exact = false, const half_t* hl = nullptr, int kind = -1) const {
-    GemmP p;
-    p.A = A, p.W = W, p.bias = bias, p.C = C, p.res = res, p.rowmap = rowmap, p.a_rowmap = a_rowmap;
-    p.M = M, p.N = N, p.K = K, p.lda = K, p.ldw = K, p.ldc = N, p.ldr = ldr, p.act = act, p.res_mod = res_mod;
-    p.out_f16 = out;
+    GemmP p = gemm_linear(A, K, W, bias, C, N, M, N, K, act, res, ldr, res_mod);
+    p.rowmap = rowmap, p.a_rowmap = a_rowmap, p.out_f16 = out;
     p.p8_wgs = eng ? (kind >= 0 && eng->gemm_wgs_kind[kind] > 0 ? eng->gemm_wgs_kind[kind] : eng->gemm_wgs) : 0;
     if (exact && hl) {   // fp32-grade on the fp16 pipe: the GEMM as a 1x1 convolution over an [1][M][1][K] image
-      p.W = hl, p.W_lo = hl + (size_t)N * K;
-      p.alpha = 1.0f / (float)(1 << F16X3_WSHIFT);
-      p.conv = 1, p.cH = M, p.cW = 1, p.cC = K, p.KH = 1, p.KW = 1, p.cstride = 1, p.cpad = 0, p.OH = M, p.OW = 1;
+      gemm_split_planes(p, hl);
       return conv_f16x3(p, s);
     }
     if (mode == 0 || exact) return gemm_f32(p, s);
     if (mode == 2) {
       p.x3 = 1, p.K = 2 * K, p.lda = 2 * K, p.ldw = 2 * K;
-      p.alpha = 1.0f / (float)(1 << F16X3_WSHIFT);
+      p.alpha = kF16x3Alpha;
       if (out == 2) p.ldc = 2 * N;
     }
     if (eng && eng->calib && kind >= 0 && mode == 1 && K <= eng->calib_ld)
@@ -285,18 +281,11 @@ int VitEngine::encode(const uint8_t* frames, int chw, int B, int H, int W, float
   const bool planes = neck2_hl && g_conv_halo && c.out_chans % 256 == 0 && c.out_chans <= 1536;
   SAMPT_TRY(layernorm_rows(neck_a, neck1w, neck1b, neck_b, Mg, c.out_chans, 1e-6f, nullptr, planes ? 3 : 0, ACT_NONE, s));
   {
-    GemmP p;
-    p.A = neck_b, p.W = neck2_w, p.C = neck_a;
-    p.M = (int)Mg, p.N = c.out_chans, p.K = 9 * c.out_chans, p.ldw = p.K, p.ldc = c.out_chans;
-    p.conv = 1, p.cH = g, p.cW = g, p.cC = c.out_chans, p.KH = 3, p.KW = 3, p.cstride = 1, p.cpad = 1, p.OH = g, p.OW = g;
-    if (neck2_hl) {
-      p.W = neck2_hl, p.W_lo = neck2_hl + (size_t)p.N * p.K;
-      p.alpha = 1.0f / (float)(1 << F16X3_WSHIFT);
-      if (planes) p.A_lo = (const half_t*)neck_b + (size_t)Mg * c.out_chans;
-      SAMPT_TRY(conv_f16x3(p, s));
-    } else {
-      SAMPT_TRY(gemm_f32(p, s));
-    }
+    const ConvW neck2{(const float*)neck2_w, nullptr, neck2_hl, c.out_chans, c.out_chans, 3, 3, 1, 1, 1};
+    Planes xp;
+    if (planes) xp.hi = (half_t*)neck_b, xp.lo = (half_t*)neck_b + (size_t)Mg * c.out_chans;
+    int oh, ow;
+    SAMPT_TRY(run_conv(neck2, neck_b, B, g, g, neck_a, 0, ACT_NONE, nullptr, oh, ow, false, s, xp));
   }
   SAMPT_TRY(layernorm_rows(neck_a, neck3w, neck3b, features, Mg, c.out_chans, 1e-6f, nullptr, 0, ACT_NONE, s));
   return SAMPT_OK;
