@@ -316,3 +316,100 @@ def name_table(named: Dict[str, torch.Tensor]):
 
 def ptr_array(ts: Sequence[torch.Tensor]):
     return (_P * len(ts))(*[t.data_ptr() for t in ts])
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# what the wrappers above the C ABI share: workspace queries, the chunk plan of a bounded workspace, engine lifetime
+# (load / check / require_hip / device_guard / name_table are looked up as module attributes when a helper RUNS, so that a
+# test double installed over them is what the helpers see)
+# ----------------------------------------------------------------------------------------------------------------------
+def workspace_bytes(name: str, *args) -> int:
+    """Bytes a ``*_workspace_bytes`` query of the C ABI reports, in either of its two forms: the size is the result, or the
+    result is a return code and the size comes back through a trailing ``size_t *`` (appended here, after ``args``)."""
+    res, argtypes = _SIGS[name]
+    fn = getattr(load(), name)
+    if res is c_size_t:
+        return int(fn(*args))
+    if not argtypes or argtypes[-1] != C.POINTER(c_size_t):
+        raise SamptError(f"{name} is not a workspace query")
+    n = c_size_t()
+    check(fn(*args, C.byref(n)), name)
+    return n.value
+
+
+def workspace(name: str, device, *args, min_bytes: int = 16) -> torch.Tensor:
+    """The uint8 scratch tensor on ``device`` that the query ``name(*args)`` asks for (``workspace_bytes``), never smaller than
+    ``min_bytes`` so that an empty problem still has a buffer to point at."""
+    return torch.empty(max(min_bytes, workspace_bytes(name, *args)), dtype=torch.uint8, device=device)
+
+
+def chunk_plan(per: int, n: int, given_bytes: Optional[int], cap: int, who: str, h: int, w: int,
+               max_chunk: Optional[int] = None) -> Tuple[int, int]:
+    """(workspace bytes, items per call) for ``n`` items that need ``per`` scratch bytes each: everything at once up to ``cap``
+    bytes unless the caller bounds the workspace, then chunks of as many items as fit (and at most ``max_chunk``).  Less than
+    one item's worth still plans one item per call: the native call itself refuses that workspace."""
+    if per == 0:
+        raise SamptError(f"{who}: h * w must be below 2^31; got {h} x {w}")
+    nbytes = max(per, min(n * per, cap)) if given_bytes is None else int(given_bytes)
+    chunk = max(1, min(n, nbytes // per))
+    if max_chunk is not None:
+        chunk = max(1, min(chunk, max_chunk))
+    return nbytes, chunk
+
+
+def create_engine(lib, symbol: str, weights: Dict[str, torch.Tensor], *args, pre=()):
+    """One ``sampt_*_create(*pre, names, ptrs, n, *args, &handle)`` over the packed ``weights`` -> the handle."""
+    names, ptrs, n = name_table(weights)
+    h = c_void_p()
+    check(getattr(lib, symbol)(*pre, names, ptrs, n, *args, C.byref(h)), symbol)
+    return h
+
+
+class EngineOwner:
+    """Lifetime of the native engines behind one Python object.  A subclass lists ``_engines`` — one (handle attribute, destroy
+    symbol) per engine — and names the attribute that records the device; handles, device and ``_lib`` stay plain attributes."""
+    _engines: Tuple[Tuple[str, str], ...] = ()
+    _engine_device = "_device"
+    engines_destroyed = 0              # handles this object has given back to the library so far
+
+    def ensure_engines(self, device, who: str, build):
+        """Engines on ``device``: nothing to do when they are there already, else ``build(lib, device)`` packs the weights,
+        calls the ``*_create`` functions and returns one handle per entry of ``_engines``.  Engines of another device (or of a
+        forgotten one, ``forget_engine_device``) are destroyed first, after that device's work has finished."""
+        old = getattr(self, self._engine_device, None)
+        live = any(getattr(self, attr, None) is not None for attr, _ in self._engines)
+        if live and old == device:
+            return
+        require_hip(device, who)
+        lib = self._lib = load()                  # (before ``build``: a handle of a build that fails half-way can still be destroyed)
+        if live:
+            old = device if old is None else old
+            with device_guard(old):
+                if getattr(old, "type", None) == "cuda":
+                    torch.cuda.synchronize(old)
+                self._destroy_engines(lib)
+            self.on_replace()
+        for (attr, _), h in zip(self._engines, build(lib, device)):
+            setattr(self, attr, h)
+        setattr(self, self._engine_device, device)
+
+    def forget_engine_device(self):
+        """The next ``ensure_engines`` replaces the engines even on the same device (they are destroyed there, after its work)."""
+        setattr(self, self._engine_device, None)
+
+    def on_replace(self):
+        """Hook: the old engines are gone — drop whatever was cached for them."""
+
+    def _destroy_engines(self, lib):
+        for attr, destroy in self._engines:
+            h = getattr(self, attr, None)
+            if h is not None:
+                getattr(lib, destroy)(h)
+                setattr(self, attr, None)
+                self.engines_destroyed += 1
+
+    def __del__(self):
+        try:
+            self._destroy_engines(self._lib)
+        except Exception:
+            pass

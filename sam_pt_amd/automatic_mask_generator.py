@@ -297,7 +297,7 @@ def nms_device(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float) 
         sc = scores.to(boxes.device).float().contiguous()
         keep = torch.empty(n, dtype=torch.int64, device=b.device)
         count = torch.empty(1, dtype=torch.int32, device=b.device)
-        ws = torch.empty(max(16, lib.sampt_amg_nms_workspace_bytes(n)), dtype=torch.uint8, device=b.device)
+        ws = _lib.workspace("sampt_amg_nms_workspace_bytes", b.device, n)
         _lib.check(lib.sampt_amg_nms(_lib.ptr(b), _lib.ptr(sc), n, float(iou_threshold), _lib.ptr(keep), _lib.ptr(count),
                                      _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "sampt_amg_nms")
         return keep[:int(count.item())]
@@ -370,37 +370,33 @@ def rle_encode_device(x: torch.Tensor, threshold: Optional[float] = None, compre
     if h == 0 or w == 0:
         raise _lib.SamptError(f"rle_encode_device: empty masks {tuple(x.shape)}")
     lib = _lib.load()
-    per = int(lib.sampt_rle_workspace_bytes(1, h, w))
-    if per == 0:
-        raise _lib.SamptError(f"rle_encode_device: h * w must be below 2^31; got {h} x {w}")
-    if workspace_bytes is None:
-        workspace_bytes = max(per, min(n * per, _RLE_WS_CAP))
-    chunk = max(1, min(n, int(workspace_bytes) // per))          # (0 masks' worth: the call itself refuses the workspace)
+    per = _lib.workspace_bytes("sampt_rle_workspace_bytes", 1, h, w)
+    workspace_bytes, chunk = _lib.chunk_plan(per, n, workspace_bytes, _RLE_WS_CAP, "rle_encode_device", h, w)
     records: List[Dict[str, Any]] = []
     with _lib.device_guard(dev):
         x = x.reshape(n, h, w)                                   # (a view when x is contiguous; slices of it keep their offset)
         if not x.is_contiguous():
             x = x.contiguous()
         stream = _lib.stream_ptr()
-        ws = torch.empty(max(16, int(workspace_bytes)), dtype=torch.uint8, device=dev)
+        ws = torch.empty(max(16, workspace_bytes), dtype=torch.uint8, device=dev)
         areas = torch.empty(n, dtype=torch.int32, device=dev)
         for c0 in range(0, n, chunk):
             c = min(chunk, n - c0)
             xc = x[c0:c0 + c]
             offsets = torch.empty(c + 1, dtype=torch.int64, device=dev)
             _lib.check(lib.sampt_rle_count(_lib.ptr(xc), int(is_f32), float(threshold or 0.0), c, h, w, _lib.ptr(offsets),
-                                           _lib.c_void_p(areas.data_ptr() + 4 * c0), _lib.ptr(ws), int(workspace_bytes), stream),
+                                           _lib.c_void_p(areas.data_ptr() + 4 * c0), _lib.ptr(ws), workspace_bytes, stream),
                        "sampt_rle_count")
             total = int(offsets[c].item())                       # host read 1: the number of runs
             counts = torch.empty(total, dtype=torch.int32, device=dev)      # (uint32 values below 2^31)
-            _lib.check(lib.sampt_rle_emit(c, h, w, _lib.ptr(offsets), _lib.ptr(counts), _lib.ptr(ws), int(workspace_bytes),
+            _lib.check(lib.sampt_rle_emit(c, h, w, _lib.ptr(offsets), _lib.ptr(counts), _lib.ptr(ws), workspace_bytes,
                                           stream), "sampt_rle_emit")
             if not compressed:
                 off = offsets.cpu().tolist()
                 flat = counts.cpu().numpy()
                 records += [{"size": [h, w], "counts": flat[off[i]:off[i + 1]].tolist()} for i in range(c)]
                 continue
-            sws = torch.empty(max(16, int(lib.sampt_rle_string_workspace_bytes(total))), dtype=torch.uint8, device=dev)
+            sws = _lib.workspace("sampt_rle_string_workspace_bytes", dev, total)
             soff = torch.empty(c + 1, dtype=torch.int64, device=dev)
             _lib.check(lib.sampt_rle_string_sizes(_lib.ptr(counts), _lib.ptr(offsets), c, total, _lib.ptr(soff), _lib.ptr(sws),
                                                   sws.numel(), stream), "sampt_rle_string_sizes")

@@ -69,11 +69,38 @@ def _prepared_entry(frames: torch.Tensor, pyr):
     return (frames, frames.data_ptr(), tuple(frames.shape), frames._version, pyr)
 
 
-def _prepared_lookup(entry, frames: torch.Tensor):
-    if entry is not None and entry[1] == frames.data_ptr() and entry[2] == tuple(frames.shape) and \
-            entry[0]._version == entry[3] and frames._version == entry[3] and entry[0].device == frames.device:
-        return entry[4]
-    return None
+def _clip_of(rgbs, batch_msg: str) -> torch.Tensor:
+    """The one clip (T,3,H,W) of ``forward``'s rgbs (1,T,3,H,W), published for the unchanged-SamPt fast path (prefetch.py)."""
+    from . import prefetch
+    prefetch.publish(rgbs[0] if rgbs.dim() == 5 else rgbs)
+    if rgbs.shape[0] != 1:
+        raise NotImplementedError(batch_msg)
+    return rgbs[0]
+
+
+def _alloc_pyramid(T: int, H0: int, W0: int, device, shard=None):
+    """The four NHWC f32 levels [T][H0 >> l][W0 >> l][128] of a clip; with ``shard`` padded to a whole number of frames per rank."""
+    Tp = T if shard is None else shard.padded_frames(T)
+    return [torch.empty((Tp, H0 >> l, W0 >> l, 128), dtype=torch.float32, device=device) for l in range(4)]
+
+
+def _pyramid_chunks(pyr, lo: int, hi: int, chunk: int):
+    """(first frame, frames, pointers of those frames' slices of every level) for frames [lo, hi) in encoder chunks."""
+    for t0 in range(lo, hi, chunk):
+        nf = min(chunk, hi - t0)
+        yield t0, nf, _lib.ptr_array([p[t0:t0 + nf] for p in pyr])
+
+
+def _sharded_encode(pyr, T: int, shard, encode):
+    """Fill ``pyr`` through ``encode(lo, hi)``: the whole clip, or with ``shard`` (sam_pt_amd.dist.FnetShard) this rank's frames
+    only, the rest arriving through ``shard.exchange`` (all_gather of the pyramid over RCCL).  -> the levels, T frames each."""
+    if shard is None:
+        encode(0, T)
+        return pyr
+    mine = shard.mine(T)
+    encode(mine.start, mine.stop)
+    shard.exchange(pyr, T, encode)
+    return [p[:T] for p in pyr]
 
 
 def load_pips_checkpoint(checkpoint_path: Optional[str]):
@@ -90,7 +117,32 @@ def load_pips_checkpoint(checkpoint_path: Optional[str]):
     return ck.get("model_state_dict", ck)
 
 
-class PipsPointTracker(PointTracker):
+class _EngineTracker(PointTracker, _lib.EngineOwner):
+    """A tracker over one native engine ``_h``: a subclass names ``_engines`` and itself (``_who``, for messages) and packs + creates in ``_build(lib, device)``."""
+    _h = None
+    _device = None
+
+    def _ensure(self, device: torch.device):
+        self.ensure_engines(device, self._who, self._build)
+
+
+class _ClipTracker(_EngineTracker):
+    """A tracker whose ``prepare`` can build a clip's feature pyramid ahead of ``forward``."""
+    _prepared = None
+    _prepared_events = None
+
+    def _prepared_pyramid(self, frames: torch.Tensor):
+        """The pyramid ``prepare`` cached for exactly this frames tensor (same storage, shape, version and device), or None."""
+        e = self._prepared
+        if e is not None and e[1] == frames.data_ptr() and e[2] == tuple(frames.shape) and \
+                e[0]._version == e[3] and frames._version == e[3] and e[0].device == frames.device:
+            return e[4]
+        return None
+
+
+class PipsPointTracker(_ClipTracker):
+    _engines, _who = (("_h", "sampt_pips_destroy"),), "PipsPointTracker"
+
     def __init__(self, checkpoint_path=None, stride=4, s=8, initial_next_frame_visibility_threshold=0.9,
                  state_dict: Optional[Dict[str, torch.Tensor]] = None, seed: int = 72, fnet_chunk: int = 8):
         super().__init__()
@@ -99,29 +151,12 @@ class PipsPointTracker(PointTracker):
         sd = state_dict if state_dict is not None else load_pips_checkpoint(checkpoint_path)
         self._sd = sd if sd is not None else init_pips_state_dict(seed)
         self.fnet_chunk = fnet_chunk
-        self._h = None
         self._w: Dict[str, torch.Tensor] = {}
-        self._device = None
         self.stats = {"windows": 0, "fnet_frames": 0}
 
-    # -- engine lifetime ---------------------------------------------------------------------
-    def _ensure(self, device: torch.device):
-        if self._h is not None and self._device == device:
-            return
-        _lib.require_hip(device, "PipsPointTracker")
-        lib = _lib.load()
+    def _build(self, lib, device):
         self._w = pack_pips(self._sd, device, self.s)
-        names, ptrs, n = _lib.name_table(self._w)
-        h = C.c_void_p()
-        _lib.check(lib.sampt_pips_create(names, ptrs, n, self.stride, self.s, C.byref(h)), "sampt_pips_create")
-        self._h, self._device, self._lib = h, device, lib
-
-    def __del__(self):
-        if getattr(self, "_h", None) is not None:
-            try:
-                self._lib.sampt_pips_destroy(self._h)
-            except Exception:
-                pass
+        return [_lib.create_engine(lib, "sampt_pips_create", self._w, self.stride, self.s)]
 
     # -- fnet + pyramid for a whole clip -----------------------------------------------------------
     @_lib.on_device(lambda self, frames, *a, **k: frames.device)
@@ -132,38 +167,28 @@ class PipsPointTracker(PointTracker):
         ``shard.exchange`` (all_gather of the pyramid over RCCL); one event for the whole pyramid."""
         self._ensure(frames.device)
         T, _, H, W = frames.shape
-        H0, W0 = H // self.stride, W // self.stride
-        Tp = T if shard is None else shard.padded_frames(T)
-        pyr = [torch.empty((Tp, H0 >> l, W0 >> l, 128), dtype=torch.float32, device=frames.device) for l in range(4)]
+        pyr = _alloc_pyramid(T, H // self.stride, W // self.stride, frames.device, shard)
         chunk = min(self.fnet_chunk, T)
-        nbytes = C.c_size_t()
-        _lib.check(self._lib.sampt_pips_fnet_workspace_bytes(self._h, chunk, H, W, C.byref(nbytes)), "fnet_workspace")
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=frames.device)
+        ws = _lib.workspace("sampt_pips_fnet_workspace_bytes", frames.device, self._h, chunk, H, W)
         frames = frames.contiguous()
+        events = chunk_events if frames.is_cuda else None
 
-        def encode(lo, hi, events=None):
-            for t0 in range(lo, hi, chunk):
-                nf = min(chunk, hi - t0)
-                outs = _lib.ptr_array([p[t0:t0 + nf] for p in pyr])
+        def encode(lo, hi):
+            for t0, nf, outs in _pyramid_chunks(pyr, lo, hi, chunk):
                 _lib.check(self._lib.sampt_pips_fnet_f32(self._h, _lib.ptr(frames[t0:t0 + nf]), nf, H, W, outs, _lib.ptr(ws),
-                                                         nbytes.value, _lib.stream_ptr()), "sampt_pips_fnet_f32")
-                if events is not None and frames.is_cuda:
+                                                         ws.numel(), _lib.stream_ptr()), "sampt_pips_fnet_f32")
+                if events is not None and shard is None:      # (a sharded pyramid gets one event for all of it, below)
                     ev = torch.cuda.Event()
                     ev.record()
                     events.append((t0, t0 + nf, ev))
                 self.stats["fnet_frames"] += nf
 
-        if shard is None:
-            encode(0, T, chunk_events)
-            return pyr
-        mine = shard.mine(T)
-        encode(mine.start, mine.stop)
-        shard.exchange(pyr, T, encode)
-        if chunk_events is not None and frames.is_cuda:
+        pyr = _sharded_encode(pyr, T, shard, encode)
+        if events is not None and shard is not None:
             ev = torch.cuda.Event()
             ev.record()
-            chunk_events.append((0, T, ev))
-        return [p[:T] for p in pyr]
+            events.append((0, T, ev))
+        return pyr
 
     # -- chained windows for a set of independent point chains (pips/tracker.py:42-153) --------------------------
     def prepare(self, frames: torch.Tensor, shard=None):
@@ -199,9 +224,7 @@ class PipsPointTracker(PointTracker):
         q_d, f_d = torch.from_numpy(q_np).to(dev), torch.from_numpy(f_np).to(dev)
         traj = torch.empty((T, N, 2), dtype=torch.float32, device=dev)
         vis = torch.empty((T, N), dtype=torch.float32, device=dev)
-        nbytes = C.c_size_t()
-        _lib.check(self._lib.sampt_pips_track_workspace_bytes(self._h, N, C.byref(nbytes)), "track_workspace")
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        ws = _lib.workspace("sampt_pips_track_workspace_bytes", dev, self._h, N)
         evs = list(chunk_events) if chunk_events else []
         ev_arr = (C.c_void_p * max(len(evs), 1))(*[e[2].cuda_event for e in evs])
         lo_arr = (C.c_int * max(len(evs), 1))(*[int(e[0]) for e in evs])
@@ -219,19 +242,15 @@ class PipsPointTracker(PointTracker):
     @torch.no_grad()
     @_lib.on_device(lambda self, rgbs, query_points: rgbs.device)
     def forward(self, rgbs, query_points):
-        from . import prefetch
-        prefetch.publish(rgbs[0] if rgbs.dim() == 5 else rgbs)    # unchanged-SamPt fast path: see prefetch.py
-        if rgbs.shape[0] != 1:
-            raise NotImplementedError("Batch size > 1 is not supported for PIPS yet")  # tracker.py:50-51
+        frames = _clip_of(rgbs, "Batch size > 1 is not supported for PIPS yet")  # tracker.py:50-51
         assert rgbs.dtype == torch.uint8, "rgbs must be uint8 (PointTracker.forward contract)"
         dev = rgbs.device
         self._ensure(dev)
-        frames = rgbs[0]
         T = frames.shape[0]
         q = query_points[0].detach().float().cpu()
         N = q.shape[0]
-        pyr = _prepared_lookup(getattr(self, "_prepared", None), frames)
-        chunk_events = getattr(self, "_prepared_events", None) if pyr is not None else None
+        pyr = self._prepared_pyramid(frames)
+        chunk_events = self._prepared_events if pyr is not None else None
         if pyr is None:
             pyr = self.compute_pyramid(frames)
         # both temporal directions are independent chains too: run them in the same rounds (tracker.py:159-167)
@@ -261,7 +280,7 @@ class PipsPointTracker(PointTracker):
         return traj.unsqueeze(0).to(dev), vis.unsqueeze(0).to(dev)
 
 
-class PipsPlusPlusPointTracker(PointTracker):
+class PipsPlusPlusPointTracker(_ClipTracker):
     """PIPS++ behind the reference constructor of
     ``sam_pt.point_tracker.pips_plus_plus.PipsPlusPlusPointTracker`` (tracker.py:11-24; configs/model/point_tracker/
     pips_plus_plus.yaml).  Differences from the reference, on purpose:
@@ -274,6 +293,7 @@ class PipsPlusPlusPointTracker(PointTracker):
       the float video feeds the encoder directly; the reference's coordinate scaling is kept verbatim, including its
       x <-> height / y <-> width mix-up (tracker.py:77-78, 126-128), which cancels on the way back.
     """
+    _engines, _who = (("_h", "sampt_pips2_destroy"),), "PipsPlusPlusPointTracker"
 
     def __init__(self, checkpoint_path=None, stride=8, max_sequence_length=128, iters=16, image_size=None,
                  state_dict: Optional[Dict[str, torch.Tensor]] = None, seed: int = 72, fnet_chunk: int = 8):
@@ -285,28 +305,12 @@ class PipsPlusPlusPointTracker(PointTracker):
         sd = state_dict if state_dict is not None else load_pips_checkpoint(checkpoint_path)
         self._sd = sd if sd is not None else init_pips2_state_dict(seed)
         self.fnet_chunk = fnet_chunk
-        self._h = None
-        self._device = None
         self.stats = {"chunks": 0, "fnet_frames": 0}
 
-    def _ensure(self, device: torch.device):
-        if self._h is not None and self._device == device:
-            return
-        _lib.require_hip(device, "PipsPlusPlusPointTracker")
+    def _build(self, lib, device):
         from .pack import pack_pips2
-        lib = _lib.load()
         self._w = pack_pips2(self._sd, device)
-        names, ptrs, n = _lib.name_table(self._w)
-        h = C.c_void_p()
-        _lib.check(lib.sampt_pips2_create(names, ptrs, n, self.stride, C.byref(h)), "sampt_pips2_create")
-        self._h, self._device, self._lib = h, device, lib
-
-    def __del__(self):
-        if getattr(self, "_h", None) is not None:
-            try:
-                self._lib.sampt_pips2_destroy(self._h)
-            except Exception:
-                pass
+        return [_lib.create_engine(lib, "sampt_pips2_create", self._w, self.stride)]
 
     @_lib.on_device(lambda self, frames, *a, **k: frames.device)
     def compute_pyramid(self, frames: torch.Tensor):
@@ -314,16 +318,11 @@ class PipsPlusPlusPointTracker(PointTracker):
         self._ensure(frames.device)
         is_f32 = 1 if frames.dtype == torch.float32 else 0
         T, _, H, W = frames.shape
-        H0, W0 = H // self.stride, W // self.stride
-        pyr = [torch.empty((T, H0 >> l, W0 >> l, 128), dtype=torch.float32, device=frames.device) for l in range(4)]
+        pyr = _alloc_pyramid(T, H // self.stride, W // self.stride, frames.device)
         chunk = min(self.fnet_chunk, T)
-        nbytes = C.c_size_t()
-        _lib.check(self._lib.sampt_pips2_fnet_workspace_bytes(self._h, chunk, H, W, C.byref(nbytes)), "fnet_workspace")
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=frames.device)
+        ws = _lib.workspace("sampt_pips2_fnet_workspace_bytes", frames.device, self._h, chunk, H, W)
         frames = frames.contiguous()
-        for t0 in range(0, T, chunk):
-            nf = min(chunk, T - t0)
-            outs = _lib.ptr_array([p[t0:t0 + nf] for p in pyr])
+        for t0, nf, outs in _pyramid_chunks(pyr, 0, T, chunk):
             _lib.check(self._lib.sampt_pips2_fnet_f32(self._h, _lib.ptr(frames[t0:t0 + nf]), is_f32, nf, H, W, outs, _lib.ptr(ws),
                                                       ws.numel(), _lib.stream_ptr()), "sampt_pips2_fnet_f32")
         self.stats["fnet_frames"] += T
@@ -357,9 +356,7 @@ class PipsPlusPlusPointTracker(PointTracker):
                 feats = [torch.empty((N, S, 128), dtype=torch.float32, device=dev) for _ in range(3)]
             else:                                                                # feat_init[:, :S_local] (tracker.py:52-54)
                 feats = [f[:, :S].contiguous() for f in feats]
-            nbytes = C.c_size_t()
-            _lib.check(self._lib.sampt_pips2_update_workspace_bytes(self._h, N, S, C.byref(nbytes)), "update_workspace")
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+            ws = _lib.workspace("sampt_pips2_update_workspace_bytes", dev, self._h, N, S)
             t0 = trajs[cur:end].contiguous()
             out = torch.empty_like(t0)
             _lib.check(self._lib.sampt_pips2_update_f32(self._h, pyr_ptrs, H0, W0, _lib.ptr(fidx), N, S, _lib.ptr(t0),
@@ -379,17 +376,13 @@ class PipsPlusPlusPointTracker(PointTracker):
     @torch.no_grad()
     @_lib.on_device(lambda self, rgbs, query_points: rgbs.device)
     def forward(self, rgbs, query_points):
-        from . import prefetch
-        prefetch.publish(rgbs[0] if rgbs.dim() == 5 else rgbs)    # unchanged-SamPt fast path: see prefetch.py
-        if rgbs.shape[0] != 1:
-            raise NotImplementedError("Only batch size 1 is supported.")          # tracker.py:83
+        frames = _clip_of(rgbs, "Only batch size 1 is supported.")               # tracker.py:83
         assert rgbs.dtype == torch.uint8, "rgbs must be uint8 (PointTracker.forward contract)"
         dev = rgbs.device
         self._ensure(dev)
-        frames = rgbs[0]
         T, _, H, W = frames.shape
         q = query_points[0].detach().float().cpu()
-        prepared = _prepared_lookup(getattr(self, "_prepared", None), frames)
+        prepared = self._prepared_pyramid(frames)
         if self.image_size is not None:                                          # tracker.py:69-78
             fr = torch.nn.functional.interpolate(frames.float() / 255.0, size=self.image_size, mode="bilinear") * 255.0
             pyr = self.compute_pyramid(fr.contiguous())
@@ -457,7 +450,7 @@ def get_points_on_a_grid(grid_size: int, interp_shape) -> torch.Tensor:
     return torch.stack([gx, gy], dim=-1)
 
 
-class CoTrackerPointTracker(PointTracker):
+class CoTrackerPointTracker(_ClipTracker):
     """CoTracker behind the constructor of ``sam_pt.point_tracker.cotracker.CoTrackerPointTracker``
     (cotracker/tracker.py:32-66; configs/model/point_tracker/cotracker.yaml) — the reference's default tracker.
 
@@ -473,6 +466,7 @@ class CoTrackerPointTracker(PointTracker):
       frames, the window-to-window carry stays on the device, nothing synchronises with the host;
     * the debug visualisation branch (cv2 / imageio, :107-142) is control plane and not built.
     """
+    _engines, _who = (("_h", "sampt_cotracker_destroy"),), "CoTrackerPointTracker"
 
     def __init__(self, checkpoint_path=None, interp_shape=(384, 512), visibility_threshold=0.7, support_grid_size=2,
                  support_grid_every_n_frames=12, add_debug_visualisations=False,
@@ -497,30 +491,16 @@ class CoTrackerPointTracker(PointTracker):
         sd = state_dict if state_dict is not None else load_cotracker_checkpoint(checkpoint_path)
         self._sd = sd if sd is not None else init_cotracker_state_dict(seed)
         self.fnet_chunk, self.iters = fnet_chunk, iters
-        self._h = None
-        self._device = None
         self._pos: Dict[Tuple[int, int], Tuple[torch.Tensor, torch.Tensor]] = {}
         self.stats = {"windows": 0, "fnet_frames": 0, "calls": 0}
 
-    def _ensure(self, device: torch.device):
-        if self._h is not None and self._device == device:
-            return
-        _lib.require_hip(device, "CoTrackerPointTracker")
+    def _build(self, lib, device):
         from .pack import pack_cotracker
-        lib = _lib.load()
         self._w = pack_cotracker(self._sd, device, self.s)
-        names, ptrs, n = _lib.name_table(self._w)
-        h = C.c_void_p()
-        _lib.check(lib.sampt_cotracker_create(names, ptrs, n, self.stride, self.s, C.byref(h)), "sampt_cotracker_create")
-        self._h, self._device, self._lib = h, device, lib
-        self._pos = {}
+        return [_lib.create_engine(lib, "sampt_cotracker_create", self._w, self.stride, self.s)]
 
-    def __del__(self):
-        if getattr(self, "_h", None) is not None:
-            try:
-                self._lib.sampt_cotracker_destroy(self._h)
-            except Exception:
-                pass
+    def on_replace(self):
+        self._pos = {}                                         # position tables of the old device
 
     # -- resize + encoder for a whole clip ---------------------------------------------------------------------
     @_lib.on_device(lambda self, frames, *a, **k: frames.device)
@@ -535,13 +515,9 @@ class CoTrackerPointTracker(PointTracker):
         frames = frames.contiguous()
         if frames.dtype != torch.uint8:
             frames = frames.float()
-        H0, W0 = h // self.stride, w // self.stride
-        Tp = T if shard is None else shard.padded_frames(T)
-        pyr = [torch.empty((Tp, H0 >> l, W0 >> l, 128), dtype=torch.float32, device=dev) for l in range(4)]
+        pyr = _alloc_pyramid(T, h // self.stride, w // self.stride, dev, shard)
         chunk = min(self.fnet_chunk, T)
-        nbytes = C.c_size_t()
-        _lib.check(self._lib.sampt_cotracker_fnet_workspace_bytes(self._h, chunk, h, w, C.byref(nbytes)), "fnet_workspace")
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        ws = _lib.workspace("sampt_cotracker_fnet_workspace_bytes", dev, self._h, chunk, h, w)
 
         def encode(lo, hi):
             if hi <= lo:
@@ -550,20 +526,12 @@ class CoTrackerPointTracker(PointTracker):
             _lib.check(self._lib.sampt_resize_frames_f32(_lib.ptr(frames[lo:hi]), 1 if frames.dtype == torch.uint8 else 0,
                                                          (hi - lo) * 3, H, W, _lib.ptr(small), h, w, _lib.stream_ptr()),
                        "sampt_resize_frames_f32")
-            for t0 in range(lo, hi, chunk):
-                nf = min(chunk, hi - t0)
-                outs = _lib.ptr_array([p[t0:t0 + nf] for p in pyr])
+            for t0, nf, outs in _pyramid_chunks(pyr, lo, hi, chunk):
                 _lib.check(self._lib.sampt_cotracker_fnet_f32(self._h, _lib.ptr(small[t0 - lo:t0 - lo + nf]), nf, h, w, outs,
-                                                              _lib.ptr(ws), nbytes.value, _lib.stream_ptr()), "sampt_cotracker_fnet_f32")
+                                                              _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "sampt_cotracker_fnet_f32")
             self.stats["fnet_frames"] += hi - lo
 
-        if shard is None:
-            encode(0, T)
-            return pyr
-        mine = shard.mine(T)
-        encode(mine.start, mine.stop)
-        shard.exchange(pyr, T, encode)
-        return [p[:T] for p in pyr]
+        return _sharded_encode(pyr, T, shard, encode)
 
     def prepare(self, frames: torch.Tensor, shard=None):
         """Build the (resized) clip's feature pyramid now, on the current stream; the next ``forward`` on the same frames
@@ -592,9 +560,7 @@ class CoTrackerPointTracker(PointTracker):
         qt_s = qt[order].to(torch.int32).contiguous()
         H0, W0 = pyr[0].shape[1:3]
         px, py = self._pos_tables(H0, W0, dev)
-        nb = C.c_size_t()
-        _lib.check(self._lib.sampt_cotracker_track_workspace_bytes(self._h, n, C.byref(nb)), "track_workspace")
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+        ws = _lib.workspace("sampt_cotracker_track_workspace_bytes", dev, self._h, n)
         traj = torch.empty((Tm, n, 2), dtype=torch.float32, device=dev)
         vis = torch.empty((Tm, n), dtype=torch.float32, device=dev)
         fmap_d, qt_d = fmap.to(dev).contiguous(), qt_s.to(dev)
@@ -611,13 +577,9 @@ class CoTrackerPointTracker(PointTracker):
     @torch.no_grad()
     @_lib.on_device(lambda self, rgbs, query_points: rgbs.device)
     def forward(self, rgbs, query_points):
-        from . import prefetch
-        prefetch.publish(rgbs[0] if rgbs.dim() == 5 else rgbs)    # unchanged-SamPt fast path: see prefetch.py
-        if rgbs.shape[0] != 1:
-            raise NotImplementedError("Batch size > 1 is not supported for CoTracker")   # the model asserts B == 1
+        frames = _clip_of(rgbs, "Batch size > 1 is not supported for CoTracker")   # the model asserts B == 1
         dev = rgbs.device
         self._ensure(dev)
-        frames = rgbs[0]
         T, _, H, W = frames.shape
         if self.interp_shape is None:                                   # tracker.py:87-88 (kept on the object)
             self.interp_shape = (H, W)
@@ -631,7 +593,7 @@ class CoTrackerPointTracker(PointTracker):
             for i in range(0, T, self.support_grid_every_n_frames):
                 g = get_points_on_a_grid(self.support_grid_size, (h, w))
                 q = torch.cat([q, torch.cat([torch.full((g.shape[0], 1), float(i)), g], dim=1)], dim=0)
-        pyr = _prepared_lookup(getattr(self, "_prepared", None), frames)
+        pyr = self._prepared_pyramid(frames)
         if pyr is None:
             pyr = self.compute_pyramid(frames)
         traj, vis = self._model(pyr, T, q, False)                       # tracker.py:104
@@ -671,7 +633,7 @@ def load_raft_checkpoint(checkpoint_path: Optional[str]):
     return {k.replace("module.", ""): v for k, v in sd.items() if k != "module"}
 
 
-class RaftPointTracker(PointTracker):
+class RaftPointTracker(_EngineTracker):
     """RAFT optical flow chained into point tracks, behind the constructor of
     ``sam_pt.point_tracker.raft.RaftPointTracker`` (raft/tracker.py:17-27; configs/model/point_tracker/raft.yaml).
     ``iters`` is an extra keyword; its default is the reference's hard-coded 32 (tracker.py:40-41).
@@ -684,6 +646,7 @@ class RaftPointTracker(PointTracker):
       the four correlation levels is a single cell, ``bilinear_sampler`` divides by ``W - 1 = 0`` and the reference returns
       NaN everywhere.
     """
+    _engines, _who = (("_h", "sampt_raft_destroy"),), "RaftPointTracker"
 
     def __init__(self, checkpoint_path=None, iters: int = 32, state_dict: Optional[Dict[str, torch.Tensor]] = None,
                  seed: int = 72, max_pairs_in_flight: int = 8):
@@ -695,28 +658,12 @@ class RaftPointTracker(PointTracker):
         sd = state_dict if state_dict is not None else load_raft_checkpoint(checkpoint_path)
         self._sd = sd if sd is not None else init_raft_state_dict(seed)
         self.max_pairs_in_flight = max(1, int(max_pairs_in_flight))
-        self._h = None
-        self._device = None
         self.stats = {"pair_directions": 0, "encoded_frames": 0}
 
-    def _ensure(self, device: torch.device):
-        if self._h is not None and self._device == device:
-            return
-        _lib.require_hip(device, "RaftPointTracker")
+    def _build(self, lib, device):
         from .pack import pack_raft
-        lib = _lib.load()
         self._w = pack_raft(self._sd, device)
-        names, ptrs, n = _lib.name_table(self._w)
-        h = C.c_void_p()
-        _lib.check(lib.sampt_raft_create(names, ptrs, n, C.byref(h)), "sampt_raft_create")
-        self._h, self._device, self._lib = h, device, lib
-
-    def __del__(self):
-        if getattr(self, "_h", None) is not None:
-            try:
-                self._lib.sampt_raft_destroy(self._h)
-            except Exception:
-                pass
+        return [_lib.create_engine(lib, "sampt_raft_create", self._w)]
 
     @staticmethod
     def check_frame_size(H: int, W: int):
@@ -748,9 +695,7 @@ class RaftPointTracker(PointTracker):
         low = torch.empty((2, max(T - 1, 0), 2, Hp // 8, Wp // 8), dtype=torch.float32, device=dev) if return_low else None
         if T > 1:
             pairs = min(T - 1, workspace_pairs if workspace_pairs is not None else self.max_pairs_in_flight)
-            nbytes = C.c_size_t()
-            _lib.check(self._lib.sampt_raft_workspace_bytes(self._h, T, H, W, pairs, C.byref(nbytes)), "sampt_raft_workspace_bytes")
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+            ws = _lib.workspace("sampt_raft_workspace_bytes", dev, self._h, T, H, W, pairs)
             _lib.check(self._lib.sampt_raft_flows_f32(self._h, _lib.ptr(frames.contiguous()), T, H, W,
                                                       self.iters if iters is None else int(iters), _lib.ptr(fwd), _lib.ptr(bwd),
                                                       _lib.ptr(low), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
@@ -821,7 +766,7 @@ def register_with_reference() -> bool:
     return True
 
 
-class SuperGluePointTracker(PointTracker):
+class SuperGluePointTracker(_EngineTracker):
     """SuperPoint keypoints of frame 0 matched by SuperGlue to every later frame, independently per frame, behind the
     constructor of ``sam_pt.point_tracker.superglue.SuperGluePointTracker`` (superglue/tracker.py:24-61;
     configs/model/point_tracker/superglue.yaml).  The only tracker that needs ``set_masks`` before ``forward``.
@@ -835,6 +780,7 @@ class SuperGluePointTracker(PointTracker):
     ``matching_config[...]['checkpoint']`` absent or None: seeded random weights (``seed``).  Refused by name:
     ``resize`` other than "no resize" (the reference raises on it as well), ``max_keypoints`` other than -1, and network
     shapes other than the shipped ones."""
+    _engines, _who = (("_h", "sampt_sg_destroy"),), "SuperGluePointTracker"
 
     def __init__(self, positive_points_per_mask: int, negative_points_per_mask: int, resize, matching_config,
                  seed: int = 72, keypoint_capacity: Optional[int] = None,
@@ -879,28 +825,12 @@ class SuperGluePointTracker(PointTracker):
             self._sg_sd = torch.load(b, map_location="cpu") if b is not None else init_superglue_state_dict(seed)
         self.keypoint_capacity = keypoint_capacity
         self.masks = None
-        self._h = None
-        self._device = None
         self.stats = {"frames": 0, "pairs": 0, "host_syncs": 0, "keypoints": []}
 
-    def _ensure(self, device: torch.device):
-        if self._h is not None and self._device == device:
-            return
-        _lib.require_hip(device, "SuperGluePointTracker")
+    def _build(self, lib, device):
         from .pack import pack_superglue
-        lib = _lib.load()
         self._w = pack_superglue(self._sp_sd, self._sg_sd, device)
-        names, ptrs, n = _lib.name_table(self._w)
-        h = C.c_void_p()
-        _lib.check(lib.sampt_sg_create(names, ptrs, n, C.byref(h)), "sampt_sg_create")
-        self._h, self._device, self._lib = h, device, lib
-
-    def __del__(self):
-        if getattr(self, "_h", None) is not None:
-            try:
-                self._lib.sampt_sg_destroy(self._h)
-            except Exception:
-                pass
+        return [_lib.create_engine(lib, "sampt_sg_create", self._w)]
 
     def set_masks(self, masks):
         """masks (n_masks, H, W) with values in {0, 1}: the query masks of the clip's first frame, at the frames' own size."""
@@ -946,10 +876,9 @@ class SuperGluePointTracker(PointTracker):
 
     def match_workspace(self, det):
         n0, n1 = det["counts"][0], max(det["counts"][1:], default=0)
-        nbytes = C.c_size_t()
-        _lib.check(self._lib.sampt_sg_workspace_bytes(self._h, 1, det["hw"][0], det["hw"][1], n0, n1, None, C.byref(nbytes)),
-                   "sampt_sg_workspace_bytes")
-        return torch.empty(max(nbytes.value, 256), dtype=torch.uint8, device=det["kpts"].device)
+        # (the query's first size, detect's, is not asked for; the helper appends the out-parameter of the second, match's)
+        return _lib.workspace("sampt_sg_workspace_bytes", det["kpts"].device, self._h, 1, det["hw"][0], det["hw"][1], n0, n1, None,
+                              min_bytes=256)
 
     @torch.no_grad()
     @_lib.on_device(lambda self, det, *a, **k: det["kpts"].device)

@@ -231,16 +231,13 @@ def shi_tomasi_device(image: torch.Tensor, mask: torch.Tensor, n_points: int, de
     without a host round trip; one download of (n, 2) corners + 16 ints at the end.  Bit-identical to the host functions above
     (tests/test_gpu_kernels.py::test_shi_tomasi_device_equals_host_restatement).  -> (corners (n_found, 2) float32 (x, y) on the
     host, info dict: k of the erosion kept (-1 = the mask itself), eroded pixel count / bounding box)."""
-    import ctypes as C
     from . import _lib
     lib = _lib.load()
     H, W = int(mask.shape[0]), int(mask.shape[1])
     with _lib.device_guard(torch.device(device)):
         img = image.to(device=device, dtype=torch.uint8).contiguous()
         m = (mask > 0).to(torch.uint8).contiguous().to(device)
-        nb = C.c_size_t()
-        _lib.check(lib.sampt_qp_corners_workspace_bytes(H, W, C.byref(nb)), "sampt_qp_corners_workspace_bytes")
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=device)
+        ws = _lib.workspace("sampt_qp_corners_workspace_bytes", device, H, W)
         xy = torch.zeros((n_points, 2), dtype=torch.float32, device=device)
         info = torch.zeros(16, dtype=torch.int32, device=device)
         _lib.check(lib.sampt_qp_shi_tomasi(_lib.ptr(img), _lib.ptr(m), H, W, int(n_points), float(quality_level), _lib.ptr(xy),

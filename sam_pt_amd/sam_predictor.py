@@ -242,8 +242,10 @@ class SamHip(nn.Module):
         return self.pixel_mean.device
 
 
-class SamPredictor:
+class SamPredictor(_lib.EngineOwner):
     max_prompt_points = 4000          # SAMPT_DEC_MAX_POINTS (include/sampt_hip.h)
+    _engines = (("_vit", "sampt_vit_destroy"), ("_dec", "sampt_dec_destroy"))
+    _engine_device = "_dev"
 
     def __init__(self, sam_model: SamHip):
         self.model = sam_model
@@ -283,24 +285,19 @@ class SamPredictor:
     # -- engines -------------------------------------------------------------------------------------
     @_lib.on_device(lambda self, *a, **k: self.model.device)
     def _ensure(self):
-        dev = self.model.device
-        if self._vit is not None and self._dev == dev:
-            return
-        _lib.require_hip(dev, "SamPredictor")
-        lib = _lib.load()
-        if self._vit is not None:      # the model moved to another device: engines, scratch and caches of the old one go
-            with _lib.device_guard(self._dev):
-                torch.cuda.synchronize(self._dev)
-                lib.sampt_vit_destroy(self._vit)
-                lib.sampt_dec_destroy(self._dec)
-            self._vit = self._dec = None
-            self._ws_vit, self._ws_dec, self._ws_hq = {}, {}, None
-            self._ws_pts = self._ws_score = None
-            self._stage.clear()
-            self._dead_cache.clear()
-            self._bias_orig, self._bias_live = None, None
-            self._bias_sets.clear()
-            self.reset_image()
+        self.ensure_engines(self.model.device, "SamPredictor", self._build)
+
+    def on_replace(self):
+        """The model moved to another device: scratch and caches of the old one go with its engines."""
+        self._ws_vit, self._ws_dec, self._ws_hq = {}, {}, None
+        self._ws_pts = self._ws_score = None
+        self._stage.clear()
+        self._dead_cache.clear()
+        self._bias_orig, self._bias_live = None, None
+        self._bias_sets.clear()
+        self.reset_image()
+
+    def _build(self, lib, dev):
         cfg, m = self.model.cfg, self.model
         f16 = {"f32": 0, "f16": 1, "f16x3": 2}[m.precision]
         self._wv = pack_vit(m.sd, cfg, dev, f16, m.max_batch)
@@ -311,25 +308,11 @@ class SamPredictor:
         c.f16 = f16
         for i in range(3):
             c.pixel_mean[i], c.pixel_std[i] = cfg.pixel_mean[i], cfg.pixel_std[i]
-        names, ptrs, n = _lib.name_table(self._wv)
-        h = C.c_void_p()
-        _lib.check(lib.sampt_vit_create(C.byref(c), names, ptrs, n, m.max_batch, C.byref(h)), "sampt_vit_create")
-        self._vit = h
+        # (the encoder's handle is stored at once: should the decoder fail to build, ``__del__`` or the next ``_ensure`` destroys it)
+        self._vit = _lib.create_engine(lib, "sampt_vit_create", self._wv, m.max_batch, pre=(C.byref(c),))
         self._wd = pack_decoder(m.sd, cfg, dev, m.max_decode_batch, hq=m.hq)
-        names, ptrs, n = _lib.name_table(self._wd)
-        h2 = C.c_void_p()
-        _lib.check(lib.sampt_dec_create(names, ptrs, n, cfg.grid, cfg.img_size, m.max_decode_batch,
-                                        cfg.embed_dim if m.hq else 0, C.byref(h2)), "sampt_dec_create")
-        self._dec, self._dev, self._lib = h2, dev, lib
-
-    def __del__(self):
-        try:
-            if self._vit is not None:
-                self._lib.sampt_vit_destroy(self._vit)
-            if self._dec is not None:
-                self._lib.sampt_dec_destroy(self._dec)
-        except Exception:
-            pass
+        return self._vit, _lib.create_engine(lib, "sampt_dec_create", self._wd, cfg.grid, cfg.img_size, m.max_decode_batch,
+                                             cfg.embed_dim if m.hq else 0)
 
     @_lib.on_device(lambda self, *a, **k: self.model.device)
     def set_gemm_workgroups(self, per_xcd):
@@ -417,9 +400,7 @@ class SamPredictor:
 
     def _vit_ws(self, B: int) -> torch.Tensor:
         if B not in self._ws_vit:
-            n = C.c_size_t()
-            _lib.check(self._lib.sampt_vit_encode_workspace_bytes(self._vit, B, C.byref(n)), "vit_workspace")
-            self._ws_vit = {B: torch.empty(n.value, dtype=torch.uint8, device=self._dev)}  # keep only the latest size
+            self._ws_vit = {B: _lib.workspace("sampt_vit_encode_workspace_bytes", self._dev, self._vit, B)}  # only the latest size
         return self._ws_vit[B]
 
     def _dead_rows(self, frames: torch.Tensor, chw: bool, H: int, W: int, ws: torch.Tensor) -> Optional[torch.Tensor]:
@@ -451,9 +432,7 @@ class SamPredictor:
         if have is None or have[0] < frames or have[1] < k:
             if have is not None:
                 frames, k = max(frames, have[0]), max(k, have[1])
-            n = C.c_size_t()
-            _lib.check(self._lib.sampt_dec_workspace_bytes_k(self._dec, frames, k, oh, ow, C.byref(n)), "dec_workspace")
-            self._ws_dec = {key: (frames, k, torch.empty(n.value, dtype=torch.uint8, device=self._dev))}
+            self._ws_dec = {key: (frames, k, _lib.workspace("sampt_dec_workspace_bytes_k", self._dev, self._dec, frames, k, oh, ow))}
         return self._ws_dec[key][2]
 
     # -- image encoder -------------------------------------------------------------------------------
@@ -502,9 +481,7 @@ class SamPredictor:
                                                       _lib.stream_ptr()), "sampt_vit_encode")
             if hq is not None:      # the ViT tap is consumed batch by batch: only the 32-channel HQ features stay resident
                 if self._ws_hq is None or self._ws_hq[0] < B:
-                    n = C.c_size_t()
-                    _lib.check(self._lib.sampt_dec_hq_workspace_bytes(self._dec, B, C.byref(n)), "hq_workspace")
-                    self._ws_hq = (B, torch.empty(n.value, dtype=torch.uint8, device=self._dev))
+                    self._ws_hq = (B, _lib.workspace("sampt_dec_hq_workspace_bytes", self._dev, self._dec, B))
                 wsh = self._ws_hq[1]
                 _lib.check(self._lib.sampt_dec_hq_features(self._dec, B, _lib.ptr(out[t0:t0 + B]), _lib.ptr(interm),
                                                            _lib.ptr(hq[t0:t0 + B]), _lib.ptr(wsh), wsh.numel(),
@@ -630,10 +607,7 @@ class SamPredictor:
     def points_workspace_bytes(self, n: int, k: int = 1) -> int:
         """Scratch bytes of one ``predict_points_batch`` chunk of n prompts with k points each."""
         self._ensure()
-        nb = C.c_size_t()
-        _lib.check(self._lib.sampt_sam_decode_points_workspace_bytes(self._dec, int(n), int(k), C.byref(nb)),
-                   "sampt_sam_decode_points_workspace_bytes")
-        return nb.value
+        return _lib.workspace_bytes("sampt_sam_decode_points_workspace_bytes", self._dec, int(n), int(k))
 
     def _decode_points(self, pts: torch.Tensor, lab: torch.Tensor, multimask: bool):
         """One sampt_sam_decode_points call: pts (n,k,2) f32 / lab (n,k) i32 contiguous on the device, n <= max_decode_batch."""
@@ -643,7 +617,7 @@ class SamPredictor:
         have = self._ws_pts
         if have is None or have[0] < n or have[1] < k:
             nn, kk = (n, k) if have is None else (max(n, have[0]), max(k, have[1]))
-            self._ws_pts = (nn, kk, torch.empty(self.points_workspace_bytes(nn, kk), dtype=torch.uint8, device=self._dev))
+            self._ws_pts = (nn, kk, _lib.workspace("sampt_sam_decode_points_workspace_bytes", self._dev, self._dec, nn, kk))
         ws = self._ws_pts[2]
         low = torch.empty((n, m, L, L), dtype=torch.float32, device=self._dev)
         iou = torch.empty((n, m), dtype=torch.float32, device=self._dev)
@@ -702,7 +676,7 @@ class SamPredictor:
         if N == 0:
             return out
         if self._ws_score is None or self._ws_score[0] < N:
-            self._ws_score = (N, torch.empty(max(1, self._lib.sampt_amg_score_workspace_bytes(N)), dtype=torch.uint8, device=dev))
+            self._ws_score = (N, _lib.workspace("sampt_amg_score_workspace_bytes", dev, N))
         ws = self._ws_score[1]
         (oh, ow), (ih, iw) = self.original_size, self.input_size
         _lib.check(self._lib.sampt_amg_score(_lib.ptr(low), N, L, self.model.cfg.img_size, ih, iw, oh, ow,

@@ -324,10 +324,9 @@ def rle_decode_device(counts_list: Sequence[Sequence[int]], h: int, w: int, devi
             counts_d = torch.from_numpy(np.ascontiguousarray(flat).view(np.int32)).to(dev) if total else \
                 torch.zeros(1, dtype=torch.int32, device=dev)
             offsets_d = torch.from_numpy(offsets).to(dev)
-            ws_bytes = int(lib.sampt_rle_decode_workspace_bytes(total))
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            ws = _lib.workspace("sampt_rle_decode_workspace_bytes", dev, total)
             _lib.check(lib.sampt_rle_decode_bits(_lib.ptr(counts_d), _lib.ptr(offsets_d), n, total, h, w, _lib.ptr(bits), _lib.ptr(area),
-                                                 _lib.ptr(status), _lib.ptr(ws), ws_bytes, _lib.stream_ptr()), "sampt_rle_decode_bits")
+                                                 _lib.ptr(status), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "sampt_rle_decode_bits")
         if as_bytes:
             by = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
             if n:
@@ -367,7 +366,7 @@ def seq_iou_counts_device(dt_bits: torch.Tensor, dt_area: torch.Tensor, dt_plane
     if gp.shape[1] != T or T == 0:
         raise _lib.SamptError(f"{who}: plane tables of one positive frame count are required; got {dp.shape} and {gp.shape}")
     lib = _lib.load()
-    ws_bytes = int(lib.sampt_seq_iou_workspace_bytes(D, G, T, h, w))
+    ws_bytes = _lib.workspace_bytes("sampt_seq_iou_workspace_bytes", D, G, T, h, w)
     if ws_bytes == 0:
         raise _lib.SamptError(f"{who}: bad shape D = {D}, G = {G}, T = {T}, {h} x {w}")
     with _lib.device_guard(dev):

@@ -278,21 +278,17 @@ def jf_counts_device(seg: torch.Tensor, ann: torch.Tensor, void: Optional[torch.
     if n == 0:
         return torch.zeros((0, 6), dtype=torch.int64, device=dev)
     lib = _lib.load()
-    per = int(lib.sampt_jf_workspace_bytes(1, h, w, r))
-    if per == 0:
-        raise _lib.SamptError(f"{who}: h * w must be below 2^31; got {h} x {w}")
-    if workspace_bytes is None:
-        workspace_bytes = max(per, min(n * per, _WS_CAP))
-    chunk = max(1, min(n, int(workspace_bytes) // per))              # (0 items' worth: the call itself refuses the workspace)
+    per = _lib.workspace_bytes("sampt_jf_workspace_bytes", 1, h, w, r)
+    workspace_bytes, chunk = _lib.chunk_plan(per, n, workspace_bytes, _WS_CAP, who, h, w)
     with _lib.device_guard(dev):
         stream = _lib.stream_ptr()
-        ws = torch.empty(max(16, int(workspace_bytes)), dtype=torch.uint8, device=dev)
+        ws = torch.empty(max(16, workspace_bytes), dtype=torch.uint8, device=dev)
         counts = torch.empty((n, 6), dtype=torch.int32, device=dev)
         for c0 in range(0, n, chunk):
             c = min(chunk, n - c0)
             va = (None, None) if V is None else (V.args(c0)[0], V.args(c0)[4])
             _lib.check(lib.sampt_jf_counts(*S.args(c0), *A.args(c0), *va, c, h, w, r, _lib.c_void_p(counts.data_ptr() + 24 * c0),
-                                           _lib.ptr(ws), int(workspace_bytes), stream), "sampt_jf_counts")
+                                           _lib.ptr(ws), workspace_bytes, stream), "sampt_jf_counts")
         return counts.to(torch.int64)
 
 
@@ -501,15 +497,13 @@ def jf_pairs_counts_device(seg: torch.Tensor, ann: torch.Tensor, void: Optional[
         return (z, torch.zeros((P, T, 2), dtype=torch.int64, device=dev), torch.zeros((K, T, 2), dtype=torch.int64, device=dev)) \
             if return_stats else z
     lib = _lib.load()
-    per = int(lib.sampt_jf_pairs_workspace_bytes(P, K, 1, h, w, r))
-    if per == 0:
+    per = _lib.workspace_bytes("sampt_jf_pairs_workspace_bytes", P, K, 1, h, w, r)
+    if per == 0:                                          # (this query has a second way to refuse: its own words)
         raise _lib.SamptError(f"{who}: h * w and 3 * P * K must be below 2^31; got {h} x {w}, P = {P}, K = {K}")
-    if workspace_bytes is None:
-        workspace_bytes = max(per, min(T * per, _WS_CAP))
-    chunk = max(1, min(T, int(workspace_bytes) // per, ((1 << 31) - 1) // (3 * P * K)))   # (0 frames' worth: the call itself refuses)
+    workspace_bytes, chunk = _lib.chunk_plan(per, T, workspace_bytes, _WS_CAP, who, h, w, max_chunk=((1 << 31) - 1) // (3 * P * K))
     with _lib.device_guard(dev):
         stream = _lib.stream_ptr()
-        ws = torch.empty(max(16, int(workspace_bytes)), dtype=torch.uint8, device=dev)
+        ws = torch.empty(max(16, workspace_bytes), dtype=torch.uint8, device=dev)
         pair = torch.empty((T, P, K, 3), dtype=torch.int32, device=dev)
         sstat = torch.empty((T, P, 2), dtype=torch.int32, device=dev)
         astat = torch.empty((T, K, 2), dtype=torch.int32, device=dev)
@@ -518,7 +512,7 @@ def jf_pairs_counts_device(seg: torch.Tensor, ann: torch.Tensor, void: Optional[
             va = (None, None) if V is None else (V.args(t0)[0], V.args(t0)[4])
             _lib.check(lib.sampt_jf_pairs_counts(*S.args(t0 * P), P, *A.args(t0 * K), K, *va, c, h, w, r,
                                                  _lib.c_void_p(pair.data_ptr() + 12 * P * K * t0), _lib.c_void_p(sstat.data_ptr() + 8 * P * t0),
-                                                 _lib.c_void_p(astat.data_ptr() + 8 * K * t0), _lib.ptr(ws), int(workspace_bytes), stream),
+                                                 _lib.c_void_p(astat.data_ptr() + 8 * K * t0), _lib.ptr(ws), workspace_bytes, stream),
                        "sampt_jf_pairs_counts")
         pair = pair.to(torch.int64).permute(1, 2, 0, 3)                   # (P, K, T, 3)
         sstat, astat = sstat.to(torch.int64).permute(1, 0, 2), astat.to(torch.int64).permute(1, 0, 2)

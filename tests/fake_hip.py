@@ -135,6 +135,18 @@ class FakeHip:
         _set(rounds, r)
         return 0
 
+    # ------------------------------------------------------------------ CoTracker (engine lifetime only)
+    def sampt_cotracker_create(self, names, ptrs, n, stride, S, out):
+        self.calls["cotracker_create"] += 1
+        return self._handle(out)
+
+    def sampt_cotracker_destroy(self, h):
+        self.calls["cotracker_destroy"] += 1
+
+    # ------------------------------------------------------------------ queries that return the size itself
+    def sampt_rle_decode_workspace_bytes(self, total):
+        return 8 * total
+
     # ------------------------------------------------------------------ SAM
     def sampt_vit_create(self, cfg_ref, names, ptrs, n, max_batch, out):
         self.calls["vit_create"] += 1
@@ -143,7 +155,7 @@ class FakeHip:
         return self._handle(out)
 
     def sampt_vit_destroy(self, h):
-        pass
+        self.calls["vit_destroy"] += 1
 
     def sampt_dec_create(self, names, ptrs, n, grid, img, max_frames, vit_dim, out):
         self.calls["dec_create"] += 1
@@ -151,7 +163,7 @@ class FakeHip:
         return self._handle(out)
 
     def sampt_dec_destroy(self, h):
-        pass
+        self.calls["dec_destroy"] += 1
 
     def sampt_vit_encode_workspace_bytes(self, h, B, out):
         _set(out, 256)
