@@ -193,6 +193,62 @@ int sampt_raft_upsample(const float* flow_low_dev, const float* mask_dev, float 
                         int W, float* out_dev, sampt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * seam 1f — TAPIR point tracker (sam_pt/point_tracker/tapir/{tracker.py:72-108, tapir_model.py, models/resnet.py,
+ * utils/model_utils.py}).  Weights under the flat names of sam_pt_amd.weights.init_tapir_state_dict after
+ * sam_pt_amd.pack.pack_tapir: convolutions [Cout][KH][KW][Cin] (the stem's Cin zero-padded 3 -> 4) with ".weight_hl" split-fp16
+ * planes where Cin % 32 == 0, "mixer.in.weight" K-padded 486 -> 496, the depthwise weights as [3][2048].
+ * The model's geometry is fixed: 256 x 256 frames, hires 64 x 64 x 128, lowres 32 x 32 x 256.  Rows are (query, frame): q * T + t.
+ *   track_f32 : frames_dev f32 (T,3,256,256) in [0, 1] (the adapter's antialiased resize of the clip / 255), query_points_dev
+ *               [n][3] = (t, x, y) in 256 x 256 pixels -> tracks_dev [n][T][2] (x, y) px, occlusion_dev / expected_dist_dev [n][T]
+ *               logits after `iters` refinements (iters >= 0; 0 = the cost-volume heads alone).  iter_out_dev (optional)
+ *               [iters + 1][n][T][4] = (x, y, occlusion, expected_dist) after the heads and after every refinement.  One call per
+ *               clip, no host synchronisation.  The refinement runs in chunks of as many queries as the workspace holds
+ *               (workspace_bytes sizes it for max_queries_in_flight; a smaller workspace means more chunks, same values).
+ *   backbone_f32 : the feature maps alone: hires_dev [nf][64][64][128], lowres_dev [nf][32][32][256], channel-normalised.
+ * Kernel-level entry points (no handle): query_feats (bilinear edge-clamped read of both maps -> [n][384] = hires | lowres),
+ * heads (one workgroup per (query, frame): weights[10] = w1 [16][9], b1, w2 [16][9], b2, w3 [16][9][32], b3, w4 [16][32], b4,
+ * w5 [2][16], b5; the 256 lowres channels of a query start at qf[q * ldq + qoff]), patch_corr (mixer input rows [n T][ldx >= 486]),
+ * temporal_mix (the mixer's time half-block; x, xo [n][T][512], ln [512], w1 / b1 / w2 / b2 [3][2048] / [2048]), gemm (act: 0 none,
+ * 1 ReLU, 3 tanh-GELU; K % 16 == 0, N % 4 == 0; every row's K order is the same whatever M is), conv2d_same_nhwc (bias-free, TensorFlow
+ * "SAME" padding — asymmetric under stride 2; dtype as for sampt_conv2d_nhwc: 0, 3 or 4) and instance_norm_affine_nhwc (scale and
+ * offset, optional ReLU; y_dev and / or y_hl_dev [2][n][hw][C] halves = the split-fp16 planes; ws of sampt_instance_norm_workspace_bytes).
+ * Every entry returns SAMPT_ERR_ARG for null pointers or non-positive counts before any launch.
+ * --------------------------------------------------------------------------------------------------------- */
+typedef struct sampt_tapir* sampt_tapir_t;
+int sampt_tapir_create(const char* const* names, const void* const* ptrs, int n, sampt_tapir_t* out);
+void sampt_tapir_destroy(sampt_tapir_t h);
+int sampt_tapir_workspace_bytes(sampt_tapir_t h, int T, int n, int max_queries_in_flight, size_t* bytes);
+int sampt_tapir_track_f32(sampt_tapir_t h, const float* frames_dev, int T, const float* query_points_dev, int n, int iters,
+                          float* tracks_dev, float* occlusion_dev, float* expected_dist_dev, float* iter_out_dev, void* workspace_dev,
+                          size_t workspace_bytes, sampt_stream_t stream);
+/* NOMINAL kernel launches of the last track_f32 call: the engine adds, per stage that really ran, the number of kernels that stage
+ * is written as (an InstanceNorm = 3: partial sums, statistics, apply; every convolution, GEMM and TAPIR kernel = 1).  It is not
+ * measured at the launch sites, so a dispatcher that splits a launch does not show.  0 for a null handle or before the first call. */
+int sampt_tapir_launches(sampt_tapir_t h);
+/* at most max_queries queries per refinement chunk even where the workspace holds more (0: no bound).  At few frames the workspace is
+ * bounded by one frame's backbone scratch, not by the chunk, so this is how a caller (or a test) asks for smaller chunks. */
+int sampt_tapir_set_max_queries(sampt_tapir_t h, int max_queries);
+int sampt_tapir_backbone_workspace_bytes(sampt_tapir_t h, int nf, size_t* bytes);
+int sampt_tapir_backbone_f32(sampt_tapir_t h, const float* frames_dev, int nf, float* hires_dev, float* lowres_dev, void* workspace_dev,
+                             size_t workspace_bytes, sampt_stream_t stream);
+int sampt_tapir_query_feats_f32(const float* hires_dev, const float* lowres_dev, int T, const float* query_points_dev, int n,
+                                float* qf_dev, sampt_stream_t stream);
+int sampt_tapir_heads_f32(const float* lowres_dev, int T, const float* qf_dev, int ldq, int qoff, const float* query_points_dev, int n,
+                          const float* const weights_dev[10], float* points_dev, float* occlusion_dev, float* expected_dist_dev,
+                          sampt_stream_t stream);
+int sampt_tapir_patch_corr_f32(const float* hires_dev, const float* lowres_dev, int T, int n, const float* pos_dev, const float* occ_dev,
+                               const float* expd_dev, const float* feat_dev, int feat_per_row, float* x_dev, int ldx, sampt_stream_t stream);
+int sampt_tapir_temporal_mix_f32(const float* x_dev, float* xo_dev, const float* ln_dev, const float* w1_dev, const float* b1_dev,
+                                 const float* w2_dev, const float* b2_dev, int n, int T, sampt_stream_t stream);
+int sampt_tapir_gemm_f32(const float* A_dev, const float* W_dev, const float* bias_dev, const float* res_dev, float* C_dev, int M, int N,
+                         int K, int act, sampt_stream_t stream);
+int sampt_conv2d_same_nhwc(int dtype, const void* x_dev, const void* w_dev, float* y_dev, int n, int H, int W, int Cin, int Cout, int K,
+                           int stride, sampt_stream_t stream);
+int sampt_instance_norm_affine_nhwc(const float* x_dev, const float* scale_dev, const float* offset_dev, float* y_dev, void* y_hl_dev,
+                                    int n, int hw, int C, float eps, int relu, void* workspace_dev, size_t workspace_bytes,
+                                    sampt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * seam 1e — SuperGlue point tracker (sam_pt/point_tracker/superglue/{tracker.py, models/superpoint.py, models/superglue.py}).
  * Weights after sam_pt_amd.pack.pack_superglue: "superpoint.<conv>.{weight,bias}" as [Cout][KH][KW][Cin] (conv1a's Cin
  * zero-padded 1 -> 4, convPb's Cout 65 -> 68), "superglue.kenc.<0..4>", "superglue.gnn.<l>.{qkv,merge,mlp0,mlp1}",

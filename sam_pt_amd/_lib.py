@@ -57,6 +57,21 @@ _SIGS = {
     "sampt_raft_corr_pyramid": (c_int, [_P, _P, c_int, c_int, C.POINTER(_P), _P, c_size_t, _P]),
     "sampt_raft_lookup": (c_int, [C.POINTER(_P), c_int, c_int, _P, C.c_long, _P, _P]),
     "sampt_raft_upsample": (c_int, [_P, _P, c_float, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "sampt_tapir_create": (c_int, [C.POINTER(c_char_p), C.POINTER(_P), c_int, C.POINTER(_P)]),
+    "sampt_tapir_destroy": (None, [_P]),
+    "sampt_tapir_workspace_bytes": (c_int, [_P, c_int, c_int, c_int, C.POINTER(c_size_t)]),
+    "sampt_tapir_track_f32": (c_int, [_P, _P, c_int, _P, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "sampt_tapir_launches": (c_int, [_P]),
+    "sampt_tapir_set_max_queries": (c_int, [_P, c_int]),
+    "sampt_tapir_backbone_workspace_bytes": (c_int, [_P, c_int, C.POINTER(c_size_t)]),
+    "sampt_tapir_backbone_f32": (c_int, [_P, _P, c_int, _P, _P, _P, c_size_t, _P]),
+    "sampt_tapir_query_feats_f32": (c_int, [_P, _P, c_int, _P, c_int, _P, _P]),
+    "sampt_tapir_heads_f32": (c_int, [_P, c_int, _P, c_int, c_int, _P, c_int, C.POINTER(_P), _P, _P, _P, _P]),
+    "sampt_tapir_patch_corr_f32": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, c_int, _P, c_int, _P]),
+    "sampt_tapir_temporal_mix_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
+    "sampt_tapir_gemm_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "sampt_conv2d_same_nhwc": (c_int, [c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "sampt_instance_norm_affine_nhwc": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, c_int, _P, c_size_t, _P]),
     "sampt_sg_create": (c_int, [C.POINTER(c_char_p), C.POINTER(_P), c_int, C.POINTER(_P)]),
     "sampt_sg_destroy": (None, [_P]),
     "sampt_sg_workspace_bytes": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, C.POINTER(c_size_t), C.POINTER(c_size_t)]),

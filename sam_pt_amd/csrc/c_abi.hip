@@ -56,6 +56,10 @@ struct sampt_pips {
 struct sampt_pips2 { Pips2Engine e; };
 struct sampt_cotracker { CotEngine e; };
 struct sampt_raft { RaftEngine e; };
+struct sampt_tapir {
+  TapirEngine e;
+  int max_queries = 0;   // > 0: at most this many queries per refinement chunk (sampt_tapir_set_max_queries)
+};
 struct sampt_sg { SgEngine e; };
 struct sampt_vit { VitEngine e; };
 // hipGraph cache of the per-(frame, object) decode chain (north_star: "hipGraph capture of the per-frame decode"): one
@@ -512,6 +516,117 @@ int sampt_raft_chain(const float* flows_fwd, const float* flows_bwd, int T, int 
                      uint8_t* vis, sampt_stream_t stream) {
   int rc = raft_chain(flows_fwd, flows_bwd, T, H, W, q, n, traj, vis, (hipStream_t)stream);
   return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_raft_chain: bad arguments") : rc;
+}
+
+// ------------------------------------------------------------------------------------------- TAPIR
+int sampt_tapir_create(const char* const* names, const void* const* ptrs, int n, sampt_tapir_t* out) {
+  if (!names || !ptrs || !out || n < 1) return fail(SAMPT_ERR_ARG, "sampt_tapir_create: bad arguments");
+  return create_handle<sampt_tapir>("sampt_tapir_create", out, [&](sampt_tapir& h) { return h.e.init(make_map(names, ptrs, n)); });
+}
+void sampt_tapir_destroy(sampt_tapir_t h) { delete h; }
+
+int sampt_tapir_workspace_bytes(sampt_tapir_t h, int T, int n, int max_queries_in_flight, size_t* bytes) {
+  if (!h || !bytes || T < 1 || n < 1 || max_queries_in_flight < 1) return fail(SAMPT_ERR_ARG, "sampt_tapir_workspace_bytes: bad arguments");
+  Arena a(nullptr, 0);
+  int rc = h->e.track(nullptr, T, nullptr, n, 1, nullptr, nullptr, nullptr, nullptr, max_queries_in_flight, a, nullptr);
+  *bytes = a.peak + 256;
+  return rc;
+}
+
+int sampt_tapir_track_f32(sampt_tapir_t h, const float* frames, int T, const float* q, int n, int iters, float* tracks, float* occ,
+                          float* expd, float* iter_out, void* ws, size_t ws_bytes, sampt_stream_t stream) {
+  if (!h || !frames || !q || !tracks || !occ || !expd || !ws || T < 1 || n < 1 || iters < 0)
+    return fail(SAMPT_ERR_ARG, "sampt_tapir_track_f32: bad arguments");
+  int qc = h->e.plan_queries(T, n, ws_bytes);
+  if (qc < 1) return fail(SAMPT_ERR_WORKSPACE, "sampt_tapir_track_f32: the workspace does not hold one query (sampt_tapir_workspace_bytes)");
+  if (h->max_queries > 0) qc = std::min(qc, h->max_queries);
+  Arena a(ws, ws_bytes);
+  return h->e.track(frames, T, q, n, iters, tracks, occ, expd, iter_out, qc, a, (hipStream_t)stream);
+}
+
+int sampt_tapir_launches(sampt_tapir_t h) { return h ? h->e.launches : 0; }
+
+int sampt_tapir_set_max_queries(sampt_tapir_t h, int max_queries) {
+  if (!h || max_queries < 0) return fail(SAMPT_ERR_ARG, "sampt_tapir_set_max_queries: bad arguments");
+  h->max_queries = max_queries;
+  return SAMPT_OK;
+}
+
+int sampt_tapir_backbone_workspace_bytes(sampt_tapir_t h, int nf, size_t* bytes) {
+  if (!h || !bytes || nf < 1) return fail(SAMPT_ERR_ARG, "sampt_tapir_backbone_workspace_bytes: bad arguments");
+  Arena a(nullptr, 0);
+  int rc = h->e.backbone(nullptr, nf, nullptr, nullptr, a, nullptr);
+  *bytes = a.peak + 256;
+  return rc;
+}
+
+int sampt_tapir_backbone_f32(sampt_tapir_t h, const float* frames, int nf, float* hires, float* lowres, void* ws, size_t ws_bytes,
+                             sampt_stream_t stream) {
+  if (!h || !frames || !hires || !lowres || !ws || nf < 1) return fail(SAMPT_ERR_ARG, "sampt_tapir_backbone_f32: bad arguments");
+  Arena a(ws, ws_bytes);
+  return h->e.backbone(frames, nf, hires, lowres, a, (hipStream_t)stream);
+}
+
+int sampt_tapir_query_feats_f32(const float* hires, const float* lowres, int T, const float* q, int n, float* qf, sampt_stream_t stream) {
+  int rc = tapir_query_feats(hires, lowres, T, q, n, qf, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_tapir_query_feats_f32: bad arguments") : rc;
+}
+
+int sampt_tapir_heads_f32(const float* lowres, int T, const float* qf, int ldq, int qoff, const float* q, int n, const float* const weights[10],
+                          float* points, float* occ, float* expd, sampt_stream_t stream) {
+  if (!weights) return fail(SAMPT_ERR_ARG, "sampt_tapir_heads_f32: bad arguments");
+  const TapirHeadW w{weights[0], weights[1], weights[2], weights[3], weights[4], weights[5], weights[6], weights[7], weights[8], weights[9]};
+  int rc = tapir_heads(lowres, T, qf, ldq, qoff, q, n, w, points, occ, expd, nullptr, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_tapir_heads_f32: bad arguments") : rc;
+}
+
+int sampt_tapir_patch_corr_f32(const float* hires, const float* lowres, int T, int n, const float* pos, const float* occ, const float* expd,
+                               const float* feat, int feat_per_row, float* x, int ldx, sampt_stream_t stream) {
+  int rc = tapir_patch_corr(hires, lowres, T, n, pos, occ, expd, feat, feat_per_row, x, ldx, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_tapir_patch_corr_f32: bad arguments") : rc;
+}
+
+int sampt_tapir_temporal_mix_f32(const float* x, float* xo, const float* ln, const float* w1, const float* b1, const float* w2, const float* b2,
+                                 int n, int T, sampt_stream_t stream) {
+  int rc = tapir_temporal_mix(x, xo, ln, w1, b1, w2, b2, n, T, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_tapir_temporal_mix_f32: bad arguments") : rc;
+}
+
+int sampt_tapir_gemm_f32(const float* A, const float* W, const float* bias, const float* res, float* C, int M, int N, int K, int act,
+                         sampt_stream_t stream) {
+  if (act != ACT_NONE && act != ACT_RELU && act != ACT_GELU_TANH) return fail(SAMPT_ERR_ARG, "sampt_tapir_gemm_f32: act must be 0, 1 or 3");
+  int rc = tapir_gemm(A, K, W, bias, C, N, M, N, K, act, res, N, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_tapir_gemm_f32: bad arguments (K % 16 == 0, N % 4 == 0, 16-byte aligned pointers)") : rc;
+}
+
+int sampt_conv2d_same_nhwc(int dtype, const void* x, const void* w, float* y, int n, int H, int W, int Cin, int Cout, int K, int stride,
+                           sampt_stream_t stream) {
+  if (!x || !w || !y || n < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || K < 1 || stride < 1 || (dtype != 0 && dtype != 3 && dtype != 4))
+    return fail(SAMPT_ERR_ARG, "sampt_conv2d_same_nhwc: bad arguments");
+  ConvW c;
+  c.w = (const float*)w, c.cin = Cin, c.cout = Cout, c.kh = c.kw = K, c.stride = stride;
+  same_padding(H, K, stride, c.ph, c.ph_after);
+  same_padding(W, K, stride, c.pw, c.pw_after);
+  if (c.pw != c.ph) return fail(SAMPT_ERR_UNSUPPORTED, "sampt_conv2d_same_nhwc: the padding before must be the same on both axes");
+  GemmP p = gemm_conv(c, x, n, H, W, y);
+  if (dtype == 0) return gemm_f32(p, (hipStream_t)stream);
+  gemm_split_planes(p, (const half_t*)w);
+  if (dtype == 4) p.A_lo = (const half_t*)x + (size_t)n * H * W * Cin;
+  return conv_f16x3(p, (hipStream_t)stream);
+}
+
+int sampt_instance_norm_affine_nhwc(const float* x, const float* scale, const float* offset, float* y, void* y_hl, int n, int hw, int C,
+                                    float eps, int relu, void* ws, size_t ws_bytes, sampt_stream_t stream) {
+  if (!x || !scale || !offset || (!y && !y_hl) || !ws || n < 1 || hw < 1 || C < 4 || C % 4)
+    return fail(SAMPT_ERR_ARG, "sampt_instance_norm_affine_nhwc: bad arguments");
+  if (ws_bytes < sampt_instance_norm_workspace_bytes(n, hw, C))
+    return fail(SAMPT_ERR_WORKSPACE, "sampt_instance_norm_affine_nhwc: workspace too small (sampt_instance_norm_workspace_bytes)");
+  Arena a(ws, ws_bytes);
+  double* part = (double*)a.get(instnorm_partial_doubles(n, hw, C) * sizeof(double));
+  float* mr = a.f32((size_t)n * C * 2);
+  SAMPT_TRY(instnorm_stats(x, n, hw, C, eps, part, mr, (hipStream_t)stream));
+  half_t* hi = (half_t*)y_hl;
+  return instnorm_affine_apply(x, mr, scale, offset, y, n, hw, C, relu, (hipStream_t)stream, hi, hi ? hi + (size_t)n * hw * C : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------- SuperGlue tracker

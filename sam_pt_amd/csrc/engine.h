@@ -51,6 +51,7 @@ struct ConvW {
   const float* b = nullptr;
   const half_t* w_hl = nullptr;  // optional: the same weights split into fp16 planes [2][Cout][K] (conv_f16x3.hip)
   int cin = 0, cout = 0, kh = 1, kw = 1, stride = 1, ph = 0, pw = 0;
+  int ph_after = -1, pw_after = -1;   // >= 0: padding after the last row / column where it differs from ph / pw (TensorFlow "SAME")
 };
 struct LinearW {
   const float *w = nullptr, *b = nullptr;   // [N][K], [N]
@@ -158,6 +159,36 @@ struct RaftEngine {
 // fmap1 [n][hw][256] with image stride s1 floats, pooled[l] [n][h_l w_l][256] with image stride s2[l]
 int raft_corr_levels(const float* fmap1, long s1, const float* const pooled[4], const long s2[4], int n, int h8, int w8,
                      float* const out[4], hipStream_t s);
+
+// TAPIR (sam_pt/point_tracker/tapir/; engine_tapir.hip): the pre-activation ResNet once per 256 x 256 frame, the cost-volume heads per
+// (query, frame), then `iters` refinements of all (query, frame) rows through the depthwise-conv mixer.  Rows are (query, frame):
+// row = q * T + t.  Weights after sam_pt_amd.pack.pack_tapir.
+struct TapirEngine {
+  struct Blk {
+    ConvW c0, c1, sc;                      // conv_0, conv_1, shortcut_conv (first block of a group only)
+    const float *n0s, *n0o, *n1s, *n1o;    // InstanceNorm scale / offset
+    bool proj;
+  } blk[4][2];
+  ConvW stem;
+  TapirHeadW head;
+  const float *in_w, *in_b, *out_w, *out_b, *ln_out, *zeros;
+  struct Mix {
+    const float *ln1, *dw1_w, *dw1_b, *dw2_w, *dw2_b, *ln2, *up_w, *up_b, *dn_w, *dn_b;
+  } mix[12];
+  std::string error;
+  int launches = 0;                        // nominal kernel launches of the last track() call that ran (engine_tapir.hip; dry passes leave it)
+
+  int init(const WeightMap& w);
+  // frames f32 (T,3,256,256) in [0, 1]; q (device [n][3]) = (t, x, y) in 256 x 256 pixels.  tracks [n][T][2] px, occ / expd [n][T]
+  // logits; iter_out (optional) [iters + 1][n][T][4] = (x, y, occlusion, expected_dist) after the heads and after every refinement.
+  // qc = queries per chunk of the refinement.
+  int track(const float* frames, int T, const float* q, int n, int iters, float* tracks, float* occ, float* expd, float* iter_out,
+            int qc, Arena& ws, hipStream_t s);
+  // feature maps of nf frames: hires [nf][64][64][128], lowres [nf][32][32][256], both divided by their channel norm
+  int backbone(const float* frames, int nf, float* hires, float* lowres, Arena& ws, hipStream_t s);
+  // the largest chunk (in queries, <= n) whose workspace fits ws_bytes; 0 if not even one query fits
+  int plan_queries(int T, int n, size_t ws_bytes);
+};
 
 // -------------------------------------------------------------------------------------------------
 // SuperPoint + SuperGlue (engine_superglue.hip).  Weights after sam_pt_amd.pack.pack_superglue.

@@ -1,6 +1,8 @@
 // Where a layer becomes a GemmP: weight loaders, descriptor builders and launchers shared by every engine and the C ABI,
 // and the BasicEncoder residual block that PIPS' and RAFT's encoders have in common.  Host code only.
 #pragma once
+#include <algorithm>
+
 #include "engine.h"
 
 namespace sampt {
@@ -17,6 +19,24 @@ inline int load_conv(const WeightMap& w, const std::string& name, int cin, int c
 }
 inline int load_conv(const WeightMap& w, const std::string& name, int cin, int cout, int k, int stride, int pad, ConvW& c) {
   return load_conv(w, name, cin, cout, k, k, stride, pad, pad, c);
+}
+
+// TensorFlow / Haiku padding "SAME" of a k x k convolution over a side x side map: total = max((ceil(side / stride) - 1) stride + k - side, 0),
+// floor(total / 2) before and the rest after
+inline void same_padding(int side, int k, int stride, int& before, int& after) {
+  const int out = (side + stride - 1) / stride, total = std::max((out - 1) * stride + k - side, 0);
+  before = total / 2, after = total - before;
+}
+// a bias-free (Haiku with_bias=False) k x k convolution with padding "SAME" over side x side maps
+inline int load_conv_same(const WeightMap& w, const std::string& name, int cin, int cout, int k, int stride, int side, ConvW& c) {
+  int b, a;
+  same_padding(side, k, stride, b, a);
+  c.w = w.f(name + ".weight");
+  c.b = nullptr;
+  c.w_hl = (cin % 32 == 0 && w.has(name + ".weight_hl")) ? w.h(name + ".weight_hl") : nullptr;
+  c.cin = cin, c.cout = cout, c.kh = c.kw = k, c.stride = stride, c.ph = c.pw = b;
+  if (a != b) c.ph_after = c.pw_after = a;
+  return c.w ? SAMPT_OK : SAMPT_ERR_ARG;
 }
 
 inline int load_linear(const WeightMap& w, const std::string& name, int n, int k, LinearW& l) {
@@ -59,7 +79,9 @@ inline GemmP gemm_linear(const void* A, int lda, const void* W, const float* bia
 // y [n][OH][OW][cout] (pixel stride ldc; 0 = cout) = conv(x [n][H][W][cin]) + bias, exact-f32 weights; OH / OW are in the result
 inline GemmP gemm_conv(const ConvW& c, const void* x, int n, int H, int W, void* y, int ldc = 0) {
   GemmP p;
-  p.OH = (H + 2 * c.ph - c.kh) / c.stride + 1, p.OW = (W + 2 * c.pw - c.kw) / c.stride + 1;
+  // the kernels index the input from the padding BEFORE (cpad) and bound-check both sides, so padding after only sets OH / OW
+  const int pha = c.ph_after >= 0 ? c.ph_after : c.ph, pwa = c.pw_after >= 0 ? c.pw_after : c.pw;
+  p.OH = (H + c.ph + pha - c.kh) / c.stride + 1, p.OW = (W + c.pw + pwa - c.kw) / c.stride + 1;
   p.A = x, p.W = c.w, p.bias = c.b, p.C = y;
   p.M = n * p.OH * p.OW, p.N = c.cout, p.K = c.kh * c.kw * c.cin, p.ldw = p.K, p.ldc = ldc ? ldc : c.cout;
   p.conv = 1, p.cH = H, p.cW = W, p.cC = c.cin, p.KH = c.kh, p.KW = c.kw, p.cstride = c.stride, p.cpad = c.ph;

@@ -207,6 +207,42 @@ int raft_upsample(const float* flow, const float* mask, float mask_scale, int h8
 int raft_chain(const float* fwd, const float* bwd, int T, int H, int W, const float* q, int n, float* traj, unsigned char* vis,
                hipStream_t s);
 
+// ---- tapir.hip (TAPIR point tracker, sam_pt/point_tracker/tapir/; layouts in the file header) ---------------------------------
+// rows are (query, frame): row = q * T + t; the model's geometry is fixed: 256 x 256 frames, hires 64 x 64 x 128, lowres 32 x 32 x 256
+struct TapirHeadW {
+  const float *w1, *b1;   // cost_volume_regression_1: [16][9], [16]
+  const float *w2, *b2;   // cost_volume_regression_2: [16][9] (input channel major), [1]
+  const float *w3, *b3;   // cost_volume_occlusion_1: [16][9][32] (output channel fastest), [32]
+  const float *w4, *b4;   // cost_volume_occlusion_2: [16][32], [16]
+  const float *w5, *b5;   // occlusion_out: [2][16], [2]
+};
+// f32 (T,3,256,256) in [0, 1] -> NHWC4 (T,256,256,4) = 2 x - 1, 4th channel 0
+int tapir_prep_frames(const float* chw, int T, float* dst, hipStream_t s);
+// y = (x - mean) * rstd * scale[c] + offset[c] (+ ReLU); y_hi / y_lo as for instnorm_apply (y == nullptr: planes only)
+int instnorm_affine_apply(const float* x, const float* mean_rstd, const float* scale, const float* offset, float* y, int nimg, long hw,
+                          int C, int relu, hipStream_t s, half_t* y_hi = nullptr, half_t* y_lo = nullptr);
+// y[row] = x[row] / sqrt(max(sum_c x[row][c]^2, 1e-12))
+int tapir_l2norm_rows(const float* x, float* y, long rows, int C, hipStream_t s);
+// qf [n][384] = hires (128) | lowres (256) read bilinearly (edge clamp) at the query (t, x, y) of frame round(t)
+int tapir_query_feats(const float* hires, const float* lowres, int T, const float* q, int n, float* qf, hipStream_t s);
+// cost-volume heads, one workgroup per (query, frame): qf rows of ldq floats whose 256 lowres channels start at qoff; pts [n T][2],
+// occ / expd [n T]; iter_out (optional) [n T][4] = (x, y, occ, expd)
+int tapir_heads(const float* lowres, int T, const float* qf, int ldq, int qoff, const float* q, int n, const TapirHeadW& w, float* pts,
+                float* occ, float* expd, float* iter_out, hipStream_t s);
+// mixer input rows x [n T][ldx >= 486]: 0, 0, occ, expd, features (384), 49 + 49 patch correlations, zeros up to ldx.  feat: [n][384]
+// (feat_per_row == 0: the query features) or [n T][384] (the previous iteration's features); pos [n T][2] in 256 x 256 pixels
+int tapir_patch_corr(const float* hires, const float* lowres, int T, int n, const float* pos, const float* occ, const float* expd,
+                     const float* feat, int feat_per_row, float* x, int ldx, hipStream_t s);
+// xo = x + sum of fours(dw2(gelu_tanh(dw1(LN(x))))) over time per query; x, xo [n][T][512], xo != x
+int tapir_temporal_mix(const float* x, float* xo, const float* ln, const float* w1, const float* b1, const float* w2, const float* b2,
+                       int n, int T, hipStream_t s);
+// C [M][N] = act(A [M][K] W [N][K]^T + bias) (+ res): exact-f32 MFMA with one K order for every row whatever M is (K % 16 == 0, N % 4 == 0)
+int tapir_gemm(const float* A, int lda, const float* W, const float* bias, float* C, int ldc, long M, int N, int K, int act,
+               const float* res, int ldr, hipStream_t s);
+// pos += res[0:2], occ += res[2], expd += res[3], feats = (first ? qf[q] : feats) + res[4:388]; iter_out (optional) [n T][4]
+int tapir_update(const float* res, const float* qf, int first, float* pos, float* occ, float* expd, float* feats, float* iter_out, int n,
+                 int T, hipStream_t s);
+
 // ---- superglue.hip (SuperGlue point tracker, sam_pt/point_tracker/superglue/; layouts in the file header) --------------------
 // uint8 (T,3,H,W) -> f32 NHWC4 (T,H,W,4): channel 0 = uint8(0.2989 r + 0.587 g + 0.114 b) / 255, the rest zero
 int sg_grey(const uint8_t* frames, int T, int H, int W, float* dst, hipStream_t s);

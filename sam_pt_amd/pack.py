@@ -276,6 +276,34 @@ def pack_raft(sd: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
     return {k: v.to(device) for k, v in out.items()}
 
 
+def pack_tapir(sd: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
+    """TAPIR (csrc/engine_tapir.hip, csrc/tapir.hip) from the names of weights.init_tapir_state_dict: the ResNet's bias-free
+    convolutions as [Cout][KH][KW][Cin] (the stem's Cin zero-padded 3 -> 4) with ``.weight_hl`` split-fp16 planes where Cin is a
+    multiple of 32 (every convolution but the stem); the heads' three convolutions in the orders the heads kernel reads —
+    hid1 [16][9], hid2 [16][9] (input channel, tap), hid3 [16][9][32] (input channel, tap, output channel); ``mixer.in.weight``
+    K-padded 486 -> 496 (16-float K steps); the depthwise weights as they are, (3, 2048); ``mixer.zeros`` = the absent LayerNorm
+    offset."""
+    out: Dict[str, torch.Tensor] = {}
+    for k, v in sd.items():
+        v = v.float()
+        if k.startswith("resnet.") and v.dim() == 4:
+            out[k] = _khwc(v, 4 if v.shape[1] == 3 else 0)
+            if v.shape[1] % 32 == 0:
+                _put_split(out, k + "_hl", out[k])
+        elif k == "heads.hid1.weight":
+            out[k] = v.reshape(16, 9).contiguous()
+        elif k == "heads.hid2.weight":
+            out[k] = v.reshape(16, 9).contiguous()
+        elif k == "heads.hid3.weight":
+            out[k] = v.permute(1, 2, 3, 0).reshape(16, 9, 32).contiguous()
+        elif k == "mixer.in.weight":
+            out[k] = torch.nn.functional.pad(v, (0, 496 - v.shape[1])).contiguous()
+        else:
+            out[k] = v.contiguous()
+    out["mixer.zeros"] = torch.zeros(512)
+    return {k: v.to(device) for k, v in out.items()}
+
+
 def fold_batchnorm1d(w: torch.Tensor, b: torch.Tensor, sd: Dict[str, torch.Tensor], bn: str, eps: float = 1e-5):
     """Conv1d(kernel 1) [out][in] followed by an eval-mode BatchNorm1d as one affine map, formed in float64 (returned as
     float64: the caller rounds once, after any further reordering)."""

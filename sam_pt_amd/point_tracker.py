@@ -739,6 +739,98 @@ class RaftPointTracker(_EngineTracker):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# TAPIR (sam_pt/point_tracker/tapir/)
+# ------------------------------------------------------------------------------------------------------------------
+TAPIR_SIZE = 256          # configs/tapir_config.py: inference.resize_height / resize_width
+
+
+class TapirPointTracker(_EngineTracker):
+    """TAPIR behind the constructor of ``sam_pt.point_tracker.tapir.TapirPointTracker`` (tapir/tracker.py:14-37;
+    configs/model/point_tracker/tapir.yaml: ``checkpoint_path``, ``visibility_threshold``).  PARITY UNPINNED: the reference model
+    needs JAX, Haiku and a checkpoint, none of which exists where this project is built; the device path is held to the
+    restatement of tests/tapir_ref.py, and ``load_tapir_checkpoint``'s key map is unverified against a real checkpoint.
+
+    ``forward`` is tracker.py:72-108: the clip / 255 goes through the same antialiased ``F.interpolate`` to 256 x 256 (on the
+    device tensor), the queries are scaled and flipped, the model runs — ONE device call per clip: the ResNet once per frame, the
+    cost-volume heads and the four refinements for all queries of the clip, any number of frames, no window chaining —, and
+    ``visibilities = (1 - sigmoid(occlusion)) * (1 - sigmoid(expected_dist)) > visibility_threshold``.  The reference's random
+    query permutation and its chunks of 64 change no value (queries are independent), so they are not reproduced."""
+    _engines, _who = (("_h", "sampt_tapir_destroy"),), "TapirPointTracker"
+
+    def __init__(self, checkpoint_path=None, visibility_threshold: float = 0.1, state_dict: Optional[Dict[str, torch.Tensor]] = None,
+                 seed: int = 72, max_queries_in_flight: int = 256):
+        super().__init__()
+        from .weights import init_tapir_state_dict, load_tapir_checkpoint
+        self.checkpoint_path, self.visibility_threshold = checkpoint_path, visibility_threshold
+        sd = state_dict if state_dict is not None else (load_tapir_checkpoint(checkpoint_path) if checkpoint_path is not None else None)
+        self._sd = sd if sd is not None else init_tapir_state_dict(seed)
+        self.max_queries_in_flight = max(1, int(max_queries_in_flight))
+        self.iters = 4                                          # num_pips_iter (tapir_model.py:267)
+        self.stats = {"clips": 0, "launches": 0}
+
+    def _build(self, lib, device):
+        from .pack import pack_tapir
+        self._w = pack_tapir(self._sd, device)
+        return [_lib.create_engine(lib, "sampt_tapir_create", self._w)]
+
+    @torch.no_grad()
+    @_lib.on_device(lambda self, frames, *a, **k: frames.device)
+    def track(self, frames: torch.Tensor, queries: torch.Tensor, iters: Optional[int] = None, return_iters: bool = False,
+              workspace_queries: Optional[int] = None):
+        """The model on one clip: frames (T,3,256,256) f32 in [0, 1] on the device, queries (N,3) = (t, x, y) in 256 x 256 pixels
+        -> tracks (N,T,2), occlusion (N,T), expected_dist (N,T) [, per-iteration (iters + 1,N,T,4) = x, y, occlusion,
+        expected_dist].  ``workspace_queries``: queries per refinement chunk (default ``max_queries_in_flight``); the workspace is sized
+        for it and the values do not depend on it."""
+        _lib.require_hip(frames.device, self._who)
+        assert frames.dtype == torch.float32 and tuple(frames.shape[1:]) == (3, TAPIR_SIZE, TAPIR_SIZE), "frames must be (T,3,256,256) f32"
+        dev = frames.device
+        self._ensure(dev)
+        T, N = frames.shape[0], queries.shape[0]
+        iters = self.iters if iters is None else int(iters)
+        q = queries.detach().to(device=dev, dtype=torch.float32).contiguous()
+        tracks = torch.empty((N, T, 2), dtype=torch.float32, device=dev)
+        occ = torch.empty((N, T), dtype=torch.float32, device=dev)
+        expd = torch.empty_like(occ)
+        its = torch.empty((iters + 1, N, T, 4), dtype=torch.float32, device=dev) if return_iters else None
+        if N > 0:
+            qc = min(N, workspace_queries if workspace_queries is not None else self.max_queries_in_flight)
+            ws = _lib.workspace("sampt_tapir_workspace_bytes", dev, self._h, T, N, qc)
+            _lib.check(self._lib.sampt_tapir_set_max_queries(self._h, qc), "sampt_tapir_set_max_queries")
+            _lib.check(self._lib.sampt_tapir_track_f32(self._h, _lib.ptr(frames.contiguous()), T, _lib.ptr(q), N, iters, _lib.ptr(tracks),
+                                                       _lib.ptr(occ), _lib.ptr(expd), _lib.ptr(its), _lib.ptr(ws), ws.numel(),
+                                                       _lib.stream_ptr()), "sampt_tapir_track_f32")
+            self.stats["clips"] += 1
+            self.stats["launches"] = int(self._lib.sampt_tapir_launches(self._h))
+        return (tracks, occ, expd, its) if return_iters else (tracks, occ, expd)
+
+    def _model(self, frames01: torch.Tensor, q_tyx: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """What the reference calls ``jitted_forward``, on our inputs: frames01 (B,T,3,256,256) in [0, 1] (the model's ``* 2 - 1``
+        happens on the device), q_tyx (B,N,3) = (t, y, x) -> tracks (B,N,T,2), occlusion, expected_dist (B,N,T)."""
+        outs = [self.track(frames01[b], q_tyx[b][:, [0, 2, 1]]) for b in range(frames01.shape[0])]      # any batch size: one clip at a time
+        return {k: torch.stack([o[i] for o in outs]) for i, k in enumerate(("tracks", "occlusion", "expected_dist"))}
+
+    @torch.no_grad()
+    @_lib.on_device(lambda self, rgbs, query_points: rgbs.device)
+    def forward(self, rgbs, query_points):
+        assert rgbs.dtype == torch.uint8, "rgbs must be uint8 (PointTracker.forward contract)"
+        B, T, _, H, W = rgbs.shape
+        size = (TAPIR_SIZE, TAPIR_SIZE)
+        rescale_hw = torch.tensor(size) / torch.tensor((H, W))
+        frames01 = torch.nn.functional.interpolate(rgbs.flatten(0, 1) / 255, size, mode="bilinear", align_corners=False,
+                                                   antialias=True).unflatten(0, (B, T))
+        q = query_points.detach().cpu().clone()
+        q[:, :, 1:] *= rescale_hw.flip(0)
+        q[:, :, 1:] = q[:, :, 1:].flip(-1)                        # (t, x, y) -> (t, y, x)
+        out = self._model(frames01, q)
+        dev = out["tracks"].device
+        expected_dist = out["expected_dist"].permute(0, 2, 1)
+        occlusion = out["occlusion"].permute(0, 2, 1)
+        visibilities = (1 - torch.sigmoid(occlusion)) * (1 - torch.sigmoid(expected_dist)) > self.visibility_threshold
+        trajectories = out["tracks"].permute(0, 2, 1, 3) / rescale_hw.flip(-1).to(dev)
+        return trajectories, visibilities
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # SuperGlue (sam_pt/point_tracker/superglue/)
 # ------------------------------------------------------------------------------------------------------------------
 SUPERPOINT_DEFAULTS = {"descriptor_dim": 256, "nms_radius": 4, "keypoint_threshold": 0.005, "max_keypoints": -1,

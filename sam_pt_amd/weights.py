@@ -505,3 +505,162 @@ def init_superglue_state_dict(seed: int = 72, gnn_scale: float = 0.1, proj_gain:
     w.uniform("final_proj.bias", (256,), 0.05)
     w.sd["bin_score"] = torch.tensor(float(bin_score))
     return w.sd
+
+
+# --------------------------------------------------------------------------------------
+# TAPIR (deepmind/tapnet @ ba1a8c8, vendored by the reference under sam_pt/point_tracker/tapir)
+# --------------------------------------------------------------------------------------
+TAPIR_GROUPS = ((64, 1), (128, 2), (256, 2), (256, 1))     # channels, stride of the four ResNet block groups
+TAPIR_MIXER_BLOCKS = 12
+TAPIR_MIXER_DIM = 512
+TAPIR_MIXER_IN = 4 + 384 + 2 * 49                          # 486
+TAPIR_MIXER_OUT = 4 + 384                                  # 388
+
+
+def init_tapir_state_dict(seed: int = 72, delta_scale: float = 0.02, logit_gain: float = 0.5, occ_gain: float = 1500.0,
+                          occ_centre: Tuple[float, float] = (0.2575, -0.2712)) -> "OrderedDict[str, torch.Tensor]":
+    """Random TAPIR weights under flat names of this project's choosing, in PyTorch layouts (``load_tapir_checkpoint`` maps a
+    Haiku checkpoint onto them):
+
+      resnet.initial_conv.weight (64,3,7,7); resnet.g<G>.b<B>.{norm0,norm1}.{scale,offset}, .{conv0,conv1}.weight (O,I,3,3) and,
+      for B = 0, .shortcut.weight (O,I,1,1) — no convolution of the ResNet has a bias;
+      heads.{hid1,hid2,hid3}.{weight,bias} (O,I,3,3), heads.{hid4,occ_out}.{weight,bias} (out,in);
+      mixer.in / mixer.out.{weight,bias} (out,in); mixer.blocks.<i>.{ln1,ln2}.scale, .{dw1,dw2}.weight (3,2048) = (tap, channel) with
+      channel 4 c + m of dw1 reading input channel c, .{dw1,dw2}.bias, .{up,down}.{weight,bias}; mixer.ln_out.scale.
+
+    CONDITIONED init, as for the other trackers.  The ResNet keeps a fan-out normal init.  The cost-volume heads of a
+    trained model turn a correlation peak into a heat-map peak; random ones do not, so ``hid1`` / ``hid2`` get a positive centre
+    tap on top of their random weights and ``hid2`` the gain ``logit_gain``: the 20 x softmax then has one clear maximum near the
+    best-correlated cell while its neighbours keep some weight, and the runner-up cell lies well below it in the logits.  The
+    occlusion head averages a ReLU map over 256 cells, so with random weights its two outputs barely move between items
+    (0.2575 +- 0.001 and -0.2712 +- 0.0005 on the golden clip): ``occlusion_out`` is re-centred on ``occ_centre`` and scaled by
+    ``occ_gain``, which spreads the logits over about +- 2 and the visibility probabilities over both sides of the 0.1 threshold.  ``delta_scale`` shrinks the mixer's output
+    head: four refinements then move a point by fractions of a pixel to a few pixels, like the trained model's, instead of
+    throwing it out of the frame, where every patch correlation is zero."""
+    w = _Init(seed)
+    w.conv("resnet.initial_conv", 64, 3, 7, 7, bias=False, kaiming_fan_out=True)
+    cin = 64
+    for g, (c, _) in enumerate(TAPIR_GROUPS):
+        for b in range(2):
+            p = f"resnet.g{g}.b{b}"
+            bc = cin if b == 0 else c
+            for n, dim in (("norm0", bc), ("norm1", c)):
+                w.normal(f"{p}.{n}.scale", (dim,), 0.05, mean=1.0)
+                w.normal(f"{p}.{n}.offset", (dim,), 0.05)
+            w.conv(p + ".conv0", c, bc, 3, 3, bias=False, kaiming_fan_out=True)
+            w.conv(p + ".conv1", c, c, 3, 3, bias=False, kaiming_fan_out=True)
+            if b == 0:
+                w.conv(p + ".shortcut", c, bc, 1, 1, bias=False, kaiming_fan_out=True)
+        cin = c
+    w.conv("heads.hid1", 16, 1, 3, 3)
+    w.conv("heads.hid2", 1, 16, 3, 3)
+    w.conv("heads.hid3", 32, 16, 3, 3)
+    w.linear("heads.hid4", 16, 32)
+    w.linear("heads.occ_out", 2, 16)
+    w.sd["heads.hid1.weight"][:, 0, 1, 1] += 1.0
+    w.sd["heads.hid2.weight"][0, :, 1, 1] += 0.5
+    w.sd["heads.hid2.weight"] *= logit_gain
+    w.sd["heads.occ_out.weight"] *= occ_gain
+    w.sd["heads.occ_out.bias"] = (w.sd["heads.occ_out.bias"] - torch.tensor(occ_centre)) * occ_gain
+    d = TAPIR_MIXER_DIM
+    w.linear("mixer.in", d, TAPIR_MIXER_IN)
+    for i in range(TAPIR_MIXER_BLOCKS):
+        p = f"mixer.blocks.{i}"
+        w.normal(p + ".ln1.scale", (d,), 0.05, mean=1.0)
+        w.uniform(p + ".dw1.weight", (3, 4 * d), 1.0 / math.sqrt(3.0))
+        w.uniform(p + ".dw1.bias", (4 * d,), 1.0 / math.sqrt(3.0))
+        w.uniform(p + ".dw2.weight", (3, 4 * d), 1.0 / math.sqrt(3.0))
+        w.uniform(p + ".dw2.bias", (4 * d,), 1.0 / math.sqrt(3.0))
+        w.normal(p + ".ln2.scale", (d,), 0.05, mean=1.0)
+        w.linear(p + ".up", 4 * d, d)
+        w.linear(p + ".down", d, 4 * d)
+    w.normal("mixer.ln_out.scale", (d,), 0.05, mean=1.0)
+    w.linear("mixer.out", TAPIR_MIXER_OUT, d)
+    w.sd["mixer.out.weight"] *= delta_scale
+    w.sd["mixer.out.bias"] *= delta_scale
+    return w.sd
+
+
+def tapir_haiku_key_map() -> "OrderedDict[str, Tuple[str, str, str]]":
+    """our name -> (Haiku module path, parameter name, layout) for every tensor the forward pass uses.
+
+    UNVERIFIED AGAINST A REAL CHECKPOINT: no TAPIR checkpoint exists where this project is built.  The paths are derived by reading
+    from Haiku's naming rules applied to tapir_model.py and models/resnet.py: a module created in its parent's ``__init__`` is
+    ``parent/~/child``, one created inside another method is ``parent/child``; repeated names get ``_1``, ``_2``, ...  So the
+    ResNet and the heads (built in ``TAPIR.__init__``) sit under ``tapir/~/``, the mixer's layers (built in its ``__call__``) under
+    ``tapir/~/pips_mlp_mixer/``, and the two depthwise convolutions of a block, both named ``mlp1_up``, are ``mlp1_up`` and
+    ``mlp1_up_1``.  Layouts: conv2d = Haiku (kh, kw, cin, cout) -> (cout, cin, kh, kw); linear = (in, out) -> (out, in);
+    dw = DepthwiseConv1D (k, 1, C * mult) -> (k, C * mult); vec = unchanged."""
+    m: "OrderedDict[str, Tuple[str, str, str]]" = OrderedDict()
+    r = "tapir/~/resnet/~/"
+    m["resnet.initial_conv.weight"] = (r + "initial_conv", "w", "conv2d")
+    for g in range(4):
+        for b in range(2):
+            hp, p = f"{r}block_group_{g}/~/block_{b}/~/", f"resnet.g{g}.b{b}."
+            for j in range(2):
+                m[f"{p}norm{j}.scale"] = (f"{hp}instancenorm_{j}", "scale", "vec")
+                m[f"{p}norm{j}.offset"] = (f"{hp}instancenorm_{j}", "offset", "vec")
+                m[f"{p}conv{j}.weight"] = (f"{hp}conv_{j}", "w", "conv2d")
+            if b == 0:
+                m[p + "shortcut.weight"] = (hp + "shortcut_conv", "w", "conv2d")
+    for ours, theirs, kind in (("hid1", "cost_volume_regression_1", "conv2d"), ("hid2", "cost_volume_regression_2", "conv2d"),
+                               ("hid3", "cost_volume_occlusion_1", "conv2d"), ("hid4", "cost_volume_occlusion_2", "linear"),
+                               ("occ_out", "occlusion_out", "linear")):
+        m[f"heads.{ours}.weight"] = ("tapir/~/" + theirs, "w", kind)
+        m[f"heads.{ours}.bias"] = ("tapir/~/" + theirs, "b", "vec")
+    x = "tapir/~/pips_mlp_mixer/"
+    for ours, theirs in (("mixer.in", "linear"), ("mixer.out", "linear_1")):
+        m[ours + ".weight"] = (x + theirs, "w", "linear")
+        m[ours + ".bias"] = (x + theirs, "b", "vec")
+    m["mixer.ln_out.scale"] = (x + "layer_norm", "scale", "vec")
+    for i in range(TAPIR_MIXER_BLOCKS):
+        hb, p = x + ("block" if i == 0 else f"block_{i}") + "/", f"mixer.blocks.{i}."
+        m[p + "ln1.scale"] = (hb + "layer_norm", "scale", "vec")
+        m[p + "ln2.scale"] = (hb + "layer_norm_1", "scale", "vec")
+        for ours, theirs, kind in (("dw1", "mlp1_up", "dw"), ("dw2", "mlp1_up_1", "dw"), ("up", "mlp2_up", "linear"),
+                                   ("down", "mlp2_down", "linear")):
+            m[f"{p}{ours}.weight"] = (hb + theirs, "w", kind)
+            m[f"{p}{ours}.bias"] = (hb + theirs, "b", "vec")
+    return m
+
+
+def load_tapir_checkpoint(path: str) -> "OrderedDict[str, torch.Tensor]":
+    """The reference's checkpoint format (tapir/tracker.py:44-45): ``np.load(path, allow_pickle=True).item()`` is
+    ``{"params": {module path: {name: array}}, "state": ...}``.  -> a state dict under this project's names and layouts
+    (``tapir_haiku_key_map``, UNVERIFIED AGAINST A REAL CHECKPOINT).  Modules the forward pass never calls (``regression_*``,
+    ``conv_stats_*``) are ignored; a tensor the map expects and the file lacks is named in the error."""
+    import numpy as np
+    ck = np.load(path, allow_pickle=True).item()
+    params = ck["params"]
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    missing = []
+    for ours, (module, name, kind) in tapir_haiku_key_map().items():
+        if module not in params or name not in params[module]:
+            missing.append(f"{module}:{name}")
+            continue
+        a = torch.from_numpy(np.asarray(params[module][name], dtype=np.float32).copy())
+        if kind == "conv2d":
+            a = a.permute(3, 2, 0, 1)
+        elif kind == "linear":
+            a = a.t()
+        elif kind == "dw":
+            a = a.reshape(a.shape[0], a.shape[-1])
+        sd[ours] = a.contiguous()
+    if missing:
+        raise KeyError(f"TAPIR checkpoint {path} lacks {len(missing)} tensors: " + ", ".join(missing[:8]) + (" ..." if len(missing) > 8 else ""))
+    return sd
+
+
+def tapir_state_dict_to_haiku(sd: Dict[str, torch.Tensor]) -> Dict[str, Dict[str, "object"]]:
+    """The inverse of ``load_tapir_checkpoint``'s mapping: the ``params`` tree of a checkpoint file holding ``sd`` (round-trip tests)."""
+    params: Dict[str, Dict[str, object]] = {}
+    for ours, (module, name, kind) in tapir_haiku_key_map().items():
+        a = sd[ours]
+        if kind == "conv2d":
+            a = a.permute(2, 3, 1, 0)
+        elif kind == "linear":
+            a = a.t()
+        elif kind == "dw":
+            a = a.reshape(a.shape[0], 1, a.shape[1])
+        params.setdefault(module, {})[name] = a.contiguous().numpy()
+    return params
