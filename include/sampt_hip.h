@@ -249,6 +249,45 @@ int sampt_instance_norm_affine_nhwc(const float* x_dev, const float* scale_dev, 
                                     sampt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * seam 1g — TapNet point tracker (sam_pt/point_tracker/tapnet/{tracker.py:67-103, tapnet_model.py, models/tsm_resnet.py,
+ * models/tsm_utils.py}).  Weights under the flat names of sam_pt_amd.weights.init_tapnet_state_dict after
+ * sam_pt_amd.pack.pack_tapnet: convolutions [Cout][KH][KW][Cin] (the stem's Cin zero-padded 3 -> 4) with ".weight_hl" split-fp16
+ * planes where Cin % 32 == 0, every BatchNorm folded into "<norm>.a" / "<norm>.b", the heads as for TAPIR with occ_out [1][16].
+ * The model's geometry is fixed: 256 x 256 frames, a 32 x 32 x 256 grid per frame.  Rows are (query, frame): q * T + t.
+ *   track_f32 : frames_dev f32 (T,3,256,256) in [0, 1] (the adapter's antialiased resize of the clip / 255), query_points_dev
+ *               [n][3] = (t, x, y) in 256 x 256 pixels -> tracks_dev [n][T][2] (x, y) px, occlusion_dev [n][T] logits.  One call
+ *               per clip for any T >= 1 (at most 4096), no host synchronisation; every block of the backbone takes all T frames in
+ *               one launch per kernel, the stem and the max-pool run in chunks of frames (set_stem_chunk, default 8; same values).
+ *   backbone_f32 : the grid alone, grid_dev [nf][32][32][256], channel-normalised.  stages_dev (optional, each entry optional):
+ *               the max-pooled stem [nf][64][64][64] and the raw outputs of units 0, 1, 2 ([nf][64][64][64], [nf][32][32][128],
+ *               [nf][32][32][256]).  The nf frames are ONE clip: the temporal shift couples neighbours.
+ * Kernel-level entry points (no handle): bn_shift (relu(a[c] x + b[c]) of x [T][hw][C], shifted in time by n_shift channels each
+ * way -> shifted_dev f32 and / or shifted_hl_dev [2][T][hw][C] halves = the split-fp16 planes; the same map unshifted -> unshifted_dev
+ * / unshifted_hl_dev where given), maxpool_nhwc (3 x 3, stride 2, "SAME"; y [n][ceil(H/2)][ceil(W/2)][C]), query_feats (trilinear,
+ * every index clamped -> [n][256]), heads (weights[10] as for sampt_tapir_heads_f32 with w5 [1][16]; temperature 10, no ReLU after w3).
+ * Every entry returns SAMPT_ERR_ARG for null pointers or non-positive counts before any launch.
+ * --------------------------------------------------------------------------------------------------------- */
+typedef struct sampt_tapnet* sampt_tapnet_t;
+int sampt_tapnet_create(const char* const* names, const void* const* ptrs, int n, sampt_tapnet_t* out);
+void sampt_tapnet_destroy(sampt_tapnet_t h);
+int sampt_tapnet_workspace_bytes(sampt_tapnet_t h, int T, int n, size_t* bytes);
+int sampt_tapnet_track_f32(sampt_tapnet_t h, const float* frames_dev, int T, const float* query_points_dev, int n, float* tracks_dev,
+                           float* occlusion_dev, void* workspace_dev, size_t workspace_bytes, sampt_stream_t stream);
+/* NOMINAL kernel launches of the last track_f32 / backbone_f32 call: 3 per stem chunk + 27 for the six blocks + 1 channel
+ * normalisation (+ 2: query features, heads).  Not measured at the launch sites.  0 for a null handle or before the first call. */
+int sampt_tapnet_launches(sampt_tapnet_t h);
+int sampt_tapnet_set_stem_chunk(sampt_tapnet_t h, int frames);
+int sampt_tapnet_backbone_workspace_bytes(sampt_tapnet_t h, int nf, size_t* bytes);
+int sampt_tapnet_backbone_f32(sampt_tapnet_t h, const float* frames_dev, int nf, float* grid_dev, float* const stages_dev[4],
+                              void* workspace_dev, size_t workspace_bytes, sampt_stream_t stream);
+int sampt_tapnet_bn_shift_f32(const float* x_dev, const float* a_dev, const float* b_dev, int T, int hw, int C, int n_shift,
+                              float* shifted_dev, void* shifted_hl_dev, float* unshifted_dev, void* unshifted_hl_dev, sampt_stream_t stream);
+int sampt_tapnet_maxpool_nhwc(const float* x_dev, float* y_dev, int n, int H, int W, int C, sampt_stream_t stream);
+int sampt_tapnet_query_feats_f32(const float* grid_dev, int T, const float* query_points_dev, int n, float* qf_dev, sampt_stream_t stream);
+int sampt_tapnet_heads_f32(const float* grid_dev, int T, const float* qf_dev, const float* query_points_dev, int n,
+                           const float* const weights_dev[10], float* points_dev, float* occlusion_dev, sampt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * seam 1e — SuperGlue point tracker (sam_pt/point_tracker/superglue/{tracker.py, models/superpoint.py, models/superglue.py}).
  * Weights after sam_pt_amd.pack.pack_superglue: "superpoint.<conv>.{weight,bias}" as [Cout][KH][KW][Cin] (conv1a's Cin
  * zero-padded 1 -> 4, convPb's Cout 65 -> 68), "superglue.kenc.<0..4>", "superglue.gnn.<l>.{qkv,merge,mlp0,mlp1}",

@@ -72,6 +72,18 @@ _SIGS = {
     "sampt_tapir_gemm_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "sampt_conv2d_same_nhwc": (c_int, [c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "sampt_instance_norm_affine_nhwc": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, c_int, _P, c_size_t, _P]),
+    "sampt_tapnet_create": (c_int, [C.POINTER(c_char_p), C.POINTER(_P), c_int, C.POINTER(_P)]),
+    "sampt_tapnet_destroy": (None, [_P]),
+    "sampt_tapnet_workspace_bytes": (c_int, [_P, c_int, c_int, C.POINTER(c_size_t)]),
+    "sampt_tapnet_track_f32": (c_int, [_P, _P, c_int, _P, c_int, _P, _P, _P, c_size_t, _P]),
+    "sampt_tapnet_launches": (c_int, [_P]),
+    "sampt_tapnet_set_stem_chunk": (c_int, [_P, c_int]),
+    "sampt_tapnet_backbone_workspace_bytes": (c_int, [_P, c_int, C.POINTER(c_size_t)]),
+    "sampt_tapnet_backbone_f32": (c_int, [_P, _P, c_int, _P, C.POINTER(_P), _P, c_size_t, _P]),
+    "sampt_tapnet_bn_shift_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    "sampt_tapnet_maxpool_nhwc": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
+    "sampt_tapnet_query_feats_f32": (c_int, [_P, c_int, _P, c_int, _P, _P]),
+    "sampt_tapnet_heads_f32": (c_int, [_P, c_int, _P, _P, c_int, C.POINTER(_P), _P, _P, _P]),
     "sampt_sg_create": (c_int, [C.POINTER(c_char_p), C.POINTER(_P), c_int, C.POINTER(_P)]),
     "sampt_sg_destroy": (None, [_P]),
     "sampt_sg_workspace_bytes": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, C.POINTER(c_size_t), C.POINTER(c_size_t)]),

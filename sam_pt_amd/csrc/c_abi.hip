@@ -60,6 +60,7 @@ struct sampt_tapir {
   TapirEngine e;
   int max_queries = 0;   // > 0: at most this many queries per refinement chunk (sampt_tapir_set_max_queries)
 };
+struct sampt_tapnet { TapnetEngine e; };
 struct sampt_sg { SgEngine e; };
 struct sampt_vit { VitEngine e; };
 // hipGraph cache of the per-(frame, object) decode chain (north_star: "hipGraph capture of the per-frame decode"): one
@@ -627,6 +628,88 @@ int sampt_instance_norm_affine_nhwc(const float* x, const float* scale, const fl
   SAMPT_TRY(instnorm_stats(x, n, hw, C, eps, part, mr, (hipStream_t)stream));
   half_t* hi = (half_t*)y_hl;
   return instnorm_affine_apply(x, mr, scale, offset, y, n, hw, C, relu, (hipStream_t)stream, hi, hi ? hi + (size_t)n * hw * C : nullptr);
+}
+
+// ------------------------------------------------------------------------------------------- TapNet
+int sampt_tapnet_create(const char* const* names, const void* const* ptrs, int n, sampt_tapnet_t* out) {
+  if (!names || !ptrs || !out || n < 1) return fail(SAMPT_ERR_ARG, "sampt_tapnet_create: bad arguments");
+  return create_handle<sampt_tapnet>("sampt_tapnet_create", out, [&](sampt_tapnet& h) { return h.e.init(make_map(names, ptrs, n)); });
+}
+void sampt_tapnet_destroy(sampt_tapnet_t h) { delete h; }
+
+int sampt_tapnet_workspace_bytes(sampt_tapnet_t h, int T, int n, size_t* bytes) {
+  if (!h || !bytes || T < 1 || n < 1) return fail(SAMPT_ERR_ARG, "sampt_tapnet_workspace_bytes: bad arguments");
+  Arena a(nullptr, 0);
+  int rc = h->e.track(nullptr, T, nullptr, n, nullptr, nullptr, a, nullptr);
+  *bytes = a.peak + 256;
+  return rc == SAMPT_OK ? rc : fail(rc, ("sampt_tapnet_workspace_bytes: " + h->e.error).c_str());
+}
+
+int sampt_tapnet_track_f32(sampt_tapnet_t h, const float* frames, int T, const float* q, int n, float* tracks, float* occ, void* ws,
+                           size_t ws_bytes, sampt_stream_t stream) {
+  if (!h || !frames || !q || !tracks || !occ || !ws || T < 1 || n < 1) return fail(SAMPT_ERR_ARG, "sampt_tapnet_track_f32: bad arguments");
+  Arena dry(nullptr, 0);
+  int rc = h->e.track(nullptr, T, nullptr, n, nullptr, nullptr, dry, nullptr);
+  if (rc != SAMPT_OK) return fail(rc, ("sampt_tapnet_track_f32: " + h->e.error).c_str());
+  if (dry.peak + 256 > ws_bytes) return fail(SAMPT_ERR_WORKSPACE, "sampt_tapnet_track_f32: workspace too small (sampt_tapnet_workspace_bytes)");
+  Arena a(ws, ws_bytes);
+  return h->e.track(frames, T, q, n, tracks, occ, a, (hipStream_t)stream);
+}
+
+int sampt_tapnet_launches(sampt_tapnet_t h) { return h ? h->e.launches : 0; }
+
+int sampt_tapnet_set_stem_chunk(sampt_tapnet_t h, int frames) {
+  if (!h || frames < 1) return fail(SAMPT_ERR_ARG, "sampt_tapnet_set_stem_chunk: bad arguments");
+  h->e.stem_chunk = frames;
+  return SAMPT_OK;
+}
+
+int sampt_tapnet_backbone_workspace_bytes(sampt_tapnet_t h, int nf, size_t* bytes) {
+  if (!h || !bytes || nf < 1) return fail(SAMPT_ERR_ARG, "sampt_tapnet_backbone_workspace_bytes: bad arguments");
+  Arena a(nullptr, 0);
+  int rc = h->e.backbone(nullptr, nf, nullptr, nullptr, a, nullptr);
+  *bytes = a.peak + 256;
+  return rc == SAMPT_OK ? rc : fail(rc, ("sampt_tapnet_backbone_workspace_bytes: " + h->e.error).c_str());
+}
+
+int sampt_tapnet_backbone_f32(sampt_tapnet_t h, const float* frames, int nf, float* grid, float* const stages[4], void* ws, size_t ws_bytes,
+                              sampt_stream_t stream) {
+  if (!h || !frames || !grid || !ws || nf < 1) return fail(SAMPT_ERR_ARG, "sampt_tapnet_backbone_f32: bad arguments");
+  Arena dry(nullptr, 0);
+  int rc = h->e.backbone(nullptr, nf, nullptr, nullptr, dry, nullptr);
+  if (rc != SAMPT_OK) return fail(rc, ("sampt_tapnet_backbone_f32: " + h->e.error).c_str());
+  if (dry.peak + 256 > ws_bytes) return fail(SAMPT_ERR_WORKSPACE, "sampt_tapnet_backbone_f32: workspace too small (sampt_tapnet_backbone_workspace_bytes)");
+  Arena a(ws, ws_bytes);
+  h->e.launches = 0;
+  return h->e.backbone(frames, nf, grid, stages, a, (hipStream_t)stream);
+}
+
+int sampt_tapnet_bn_shift_f32(const float* x, const float* a, const float* b, int T, int hw, int C, int n_shift, float* shifted,
+                              void* shifted_hl, float* unshifted, void* unshifted_hl, sampt_stream_t stream) {
+  if (!x || !a || !b || (!shifted && !shifted_hl) || T < 1 || hw < 1 || C < 4) return fail(SAMPT_ERR_ARG, "sampt_tapnet_bn_shift_f32: bad arguments");
+  const size_t el = (size_t)T * hw * C;
+  half_t *sh = (half_t*)shifted_hl, *uh = (half_t*)unshifted_hl;
+  int rc = tapnet_bn_shift(x, a, b, T, hw, C, n_shift, shifted, sh, sh ? sh + el : nullptr, unshifted, uh, uh ? uh + el : nullptr,
+                           (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_tapnet_bn_shift_f32: bad arguments (C % 4 == 0, n_shift % 4 == 0, 2 n_shift <= C)") : rc;
+}
+
+int sampt_tapnet_maxpool_nhwc(const float* x, float* y, int n, int H, int W, int C, sampt_stream_t stream) {
+  int rc = tapnet_maxpool(x, y, n, H, W, C, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_tapnet_maxpool_nhwc: bad arguments (C % 4 == 0)") : rc;
+}
+
+int sampt_tapnet_query_feats_f32(const float* grid, int T, const float* q, int n, float* qf, sampt_stream_t stream) {
+  int rc = tapnet_query_feats(grid, T, q, n, qf, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_tapnet_query_feats_f32: bad arguments") : rc;
+}
+
+int sampt_tapnet_heads_f32(const float* grid, int T, const float* qf, const float* q, int n, const float* const weights[10], float* points,
+                           float* occ, sampt_stream_t stream) {
+  if (!weights) return fail(SAMPT_ERR_ARG, "sampt_tapnet_heads_f32: bad arguments");
+  const TapirHeadW w{weights[0], weights[1], weights[2], weights[3], weights[4], weights[5], weights[6], weights[7], weights[8], weights[9]};
+  int rc = tapnet_heads(grid, T, qf, q, n, w, points, occ, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_tapnet_heads_f32: bad arguments") : rc;
 }
 
 // ------------------------------------------------------------------------------------------- SuperGlue tracker

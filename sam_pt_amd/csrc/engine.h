@@ -190,6 +190,29 @@ struct TapirEngine {
   int plan_queries(int T, int n, size_t ws_bytes);
 };
 
+// TapNet (sam_pt/point_tracker/tapnet/; engine_tapnet.hip): TSM-ResNet-18 up to unit 2 over ALL frames of the clip per launch (BatchNorm
+// in inference mode is a per-channel affine), then the query features and the cost-volume heads.  Weights after sam_pt_amd.pack.pack_tapnet.
+struct TapnetEngine {
+  struct Blk {
+    ConvW c0, c2, sc;                      // conv_0, conv_2, shortcut_conv (block 0 of a unit only)
+    const float *a0, *b0, *a1, *b1;        // the two folded BatchNorms
+    bool proj;
+    int shift;                             // channels shifted each way on the way to conv_0
+  } blk[3][2];
+  ConvW stem;
+  TapirHeadW head;
+  std::string error;
+  int stem_chunk = 8;                      // frames per pass of the stem and the max-pool (the 128 x 128 x 64 map exists for these only)
+  int launches = 0;                        // nominal kernel launches of the last track() that ran (engine_tapnet.hip; dry passes leave it)
+
+  int init(const WeightMap& w);
+  // frames f32 (T,3,256,256) in [0, 1]; q (device [n][3]) = (t, x, y) in 256 x 256 pixels.  tracks [n][T][2] px, occ [n][T] logits.
+  int track(const float* frames, int T, const float* q, int n, float* tracks, float* occ, Arena& ws, hipStream_t s);
+  // grid [T][32][32][256], channel-normalised.  stages (optional, each entry optional): the max-pooled stem [T][64][64][64] and the
+  // outputs of units 0, 1, 2 ([T][64][64][64], [T][32][32][128], [T][32][32][256]), copied out for tests
+  int backbone(const float* frames, int T, float* grid, float* const* stages, Arena& ws, hipStream_t s);
+};
+
 // -------------------------------------------------------------------------------------------------
 // SuperPoint + SuperGlue (engine_superglue.hip).  Weights after sam_pt_amd.pack.pack_superglue.
 struct SgDetectCfg {

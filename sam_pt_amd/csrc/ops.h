@@ -214,7 +214,7 @@ struct TapirHeadW {
   const float *w2, *b2;   // cost_volume_regression_2: [16][9] (input channel major), [1]
   const float *w3, *b3;   // cost_volume_occlusion_1: [16][9][32] (output channel fastest), [32]
   const float *w4, *b4;   // cost_volume_occlusion_2: [16][32], [16]
-  const float *w5, *b5;   // occlusion_out: [2][16], [2]
+  const float *w5, *b5;   // occlusion_out: [2][16], [2] (TapNet: [1][16], [1])
 };
 // f32 (T,3,256,256) in [0, 1] -> NHWC4 (T,256,256,4) = 2 x - 1, 4th channel 0
 int tapir_prep_frames(const float* chw, int T, float* dst, hipStream_t s);
@@ -242,6 +242,19 @@ int tapir_gemm(const float* A, int lda, const float* W, const float* bias, float
 // pos += res[0:2], occ += res[2], expd += res[3], feats = (first ? qf[q] : feats) + res[4:388]; iter_out (optional) [n T][4]
 int tapir_update(const float* res, const float* qf, int first, float* pos, float* occ, float* expd, float* feats, float* iter_out, int n,
                  int T, hipStream_t s);
+
+// ---- tapnet.hip (TapNet point tracker, sam_pt/point_tracker/tapnet/; layouts in the file header) -------------------------------
+// relu(a[c] x + b[c]) of x [T][hw][C] (BatchNorm folded on the host), written (1) temporally shifted by n channels — output channels
+// [0, n) = channels [C - n, C) of frame t + 1, [C - n, C) = channels [0, n) of frame t - 1, zeros past the clip's ends — to ys (f32) and /
+// or ys_hi / ys_lo (split-fp16 planes), and (2) unshifted to yu and / or yu_hi / yu_lo where given.  n % 4 == 0, 2 n <= C; n = 0: no shift.
+int tapnet_bn_shift(const float* x, const float* a, const float* b, int T, long hw, int C, int n, float* ys, half_t* ys_hi, half_t* ys_lo,
+                    float* yu, half_t* yu_hi, half_t* yu_lo, hipStream_t s);
+// 3 x 3 max-pool, stride 2, TensorFlow "SAME" (padding never wins): x [n][H][W][C] -> y [n][ceil(H / 2)][ceil(W / 2)][C]
+int tapnet_maxpool(const float* x, float* y, int n, int H, int W, int C, hipStream_t s);
+// qf [n][256] = the grid [T][32][32][256] read trilinearly (every index clamped) at the query (t, x, y); t is not rounded
+int tapnet_query_feats(const float* grid, int T, const float* q, int n, float* qf, hipStream_t s);
+// cost-volume heads (cost_volume_heads.h: temperature 10, w5 [1][16], no ReLU after w3): qf [n][256]; pts [n T][2], occ [n T]
+int tapnet_heads(const float* grid, int T, const float* qf, const float* q, int n, const TapirHeadW& w, float* pts, float* occ, hipStream_t s);
 
 // ---- superglue.hip (SuperGlue point tracker, sam_pt/point_tracker/superglue/; layouts in the file header) --------------------
 // uint8 (T,3,H,W) -> f32 NHWC4 (T,H,W,4): channel 0 = uint8(0.2989 r + 0.587 g + 0.114 b) / 255, the rest zero

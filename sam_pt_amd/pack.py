@@ -304,6 +304,40 @@ def pack_tapir(sd: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
     return {k: v.to(device) for k, v in out.items()}
 
 
+def fold_batchnorm_affine(sd: Dict[str, torch.Tensor], bn: str, eps: float = 1e-5):
+    """An inference-mode BatchNorm as y = a x + b per channel: a = scale * rsqrt(var + eps), b = offset - mean * a, formed in the
+    dtype of the statistics (float32 for a packed model; tests/tapnet_ref.py folds the same way in its own dtype)."""
+    a = sd[bn + ".scale"] * torch.rsqrt(sd[bn + ".var"] + eps)
+    return a, sd[bn + ".offset"] - sd[bn + ".mean"] * a
+
+
+def pack_tapnet(sd: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
+    """TapNet (csrc/engine_tapnet.hip, csrc/tapnet.hip) from the names of weights.init_tapnet_state_dict: the backbone's bias-free
+    convolutions as [Cout][KH][KW][Cin] (the stem's Cin zero-padded 3 -> 4) with ``.weight_hl`` split-fp16 planes where Cin is a
+    multiple of 32 (every convolution but the stem); each BatchNorm folded into ``<norm>.a`` / ``<norm>.b``; the heads' three
+    convolutions in the orders the heads kernel reads, as for TAPIR."""
+    out: Dict[str, torch.Tensor] = {}
+    for k, v in sd.items():
+        v = v.float()
+        if k.startswith("tsm.") and v.dim() == 4:
+            out[k] = _khwc(v, 4 if v.shape[1] == 3 else 0)
+            if v.shape[1] % 32 == 0:
+                _put_split(out, k + "_hl", out[k])
+        elif k.startswith("tsm.") and k.endswith(".scale"):
+            bn = k[:-len(".scale")]
+            a, b = fold_batchnorm_affine({n: t.float() for n, t in sd.items() if n.startswith(bn + ".")}, bn)
+            out[bn + ".a"], out[bn + ".b"] = a.contiguous(), b.contiguous()
+        elif k.startswith("tsm."):
+            continue                                           # offset, mean, var: folded above
+        elif k in ("heads.hid1.weight", "heads.hid2.weight"):
+            out[k] = v.reshape(16, 9).contiguous()
+        elif k == "heads.hid3.weight":
+            out[k] = v.permute(1, 2, 3, 0).reshape(16, 9, 32).contiguous()
+        else:
+            out[k] = v.contiguous()
+    return {k: v.to(device) for k, v in out.items()}
+
+
 def fold_batchnorm1d(w: torch.Tensor, b: torch.Tensor, sd: Dict[str, torch.Tensor], bn: str, eps: float = 1e-5):
     """Conv1d(kernel 1) [out][in] followed by an eval-mode BatchNorm1d as one affine map, formed in float64 (returned as
     float64: the caller rounds once, after any further reordering)."""

@@ -831,6 +831,88 @@ class TapirPointTracker(_EngineTracker):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# TapNet (sam_pt/point_tracker/tapnet/)
+# ------------------------------------------------------------------------------------------------------------------
+TAPNET_SIZE = 256         # configs/tapnet_config.py: inference.resize_height / resize_width
+
+
+class TapnetPointTracker(_EngineTracker):
+    """TapNet behind the constructor of ``sam_pt.point_tracker.tapnet.TapnetPointTracker`` (tapnet/tracker.py:13-36;
+    configs/model/point_tracker/tapnet.yaml: ``checkpoint_path``, ``visibility_threshold``).  PARITY UNPINNED: the reference model
+    needs JAX, Haiku and a checkpoint, none of which exists where this project is built; the device path is held to the
+    restatement of tests/tapnet_ref.py, and ``load_tapnet_checkpoint``'s key map is unverified against a real checkpoint.
+
+    Only the adapter's configuration is built: TSM-ResNet-18 up to unit 2 at output stride 8 on a 5-D input (``tsm_mode='gpu'``,
+    ``num_frames`` = the clip's length), one head, 256 x 256 frames.
+
+    ``forward`` is tracker.py:67-103: the clip / 255 goes through the same antialiased ``F.interpolate`` to 256 x 256 (on the
+    device tensor), the queries are scaled and flipped, the model runs — ONE device call per clip, every block of the backbone over
+    all frames at once —, and ``visibilities = (1 - sigmoid(occlusion)) > visibility_threshold``.  The reference's chunks of 16
+    queries change no value (queries are independent), so they are not reproduced."""
+    _engines, _who = (("_h", "sampt_tapnet_destroy"),), "TapnetPointTracker"
+
+    def __init__(self, checkpoint_path=None, visibility_threshold: float = 0.5, state_dict: Optional[Dict[str, torch.Tensor]] = None,
+                 seed: int = 72):
+        super().__init__()
+        from .weights import init_tapnet_state_dict, load_tapnet_checkpoint
+        self.checkpoint_path, self.visibility_threshold = checkpoint_path, visibility_threshold
+        sd = state_dict if state_dict is not None else (load_tapnet_checkpoint(checkpoint_path) if checkpoint_path is not None else None)
+        self._sd = sd if sd is not None else init_tapnet_state_dict(seed)
+        self.stats = {"clips": 0, "launches": 0}
+
+    def _build(self, lib, device):
+        from .pack import pack_tapnet
+        self._w = pack_tapnet(self._sd, device)
+        return [_lib.create_engine(lib, "sampt_tapnet_create", self._w)]
+
+    @torch.no_grad()
+    @_lib.on_device(lambda self, frames, *a, **k: frames.device)
+    def track(self, frames: torch.Tensor, queries: torch.Tensor):
+        """The model on one clip: frames (T,3,256,256) f32 in [0, 1] on the device, queries (N,3) = (t, x, y) in 256 x 256 pixels
+        -> tracks (N,T,2), occlusion (N,T) logits."""
+        _lib.require_hip(frames.device, self._who)
+        assert frames.dtype == torch.float32 and tuple(frames.shape[1:]) == (3, TAPNET_SIZE, TAPNET_SIZE), "frames must be (T,3,256,256) f32"
+        dev = frames.device
+        self._ensure(dev)
+        T, N = frames.shape[0], queries.shape[0]
+        q = queries.detach().to(device=dev, dtype=torch.float32).contiguous()
+        tracks = torch.empty((N, T, 2), dtype=torch.float32, device=dev)
+        occ = torch.empty((N, T), dtype=torch.float32, device=dev)
+        if N > 0:
+            ws = _lib.workspace("sampt_tapnet_workspace_bytes", dev, self._h, T, N)
+            _lib.check(self._lib.sampt_tapnet_track_f32(self._h, _lib.ptr(frames.contiguous()), T, _lib.ptr(q), N, _lib.ptr(tracks),
+                                                        _lib.ptr(occ), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "sampt_tapnet_track_f32")
+            self.stats["clips"] += 1
+            self.stats["launches"] = int(self._lib.sampt_tapnet_launches(self._h))
+        return tracks, occ
+
+    def _model(self, frames01: torch.Tensor, q_tyx: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """What the reference calls ``jitted_forward``, on our inputs: frames01 (B,T,3,256,256) in [0, 1] (the model's ``* 2 - 1``
+        happens on the device), q_tyx (B,N,3) = (t, y, x) -> tracks (B,N,T,2), occlusion (B,N,T)."""
+        outs = [self.track(frames01[b], q_tyx[b][:, [0, 2, 1]]) for b in range(frames01.shape[0])]      # any batch size: one clip at a time
+        return {k: torch.stack([o[i] for o in outs]) for i, k in enumerate(("tracks", "occlusion"))}
+
+    @torch.no_grad()
+    @_lib.on_device(lambda self, rgbs, query_points: rgbs.device)
+    def forward(self, rgbs, query_points):
+        assert rgbs.dtype == torch.uint8, "rgbs must be uint8 (PointTracker.forward contract)"
+        B, T, _, H, W = rgbs.shape
+        size = (TAPNET_SIZE, TAPNET_SIZE)
+        rescale_hw = torch.tensor(size) / torch.tensor((H, W))
+        frames01 = torch.nn.functional.interpolate(rgbs.flatten(0, 1) / 255, size, mode="bilinear", align_corners=False,
+                                                   antialias=True).unflatten(0, (B, T))
+        q = query_points.detach().cpu().clone()
+        q[:, :, 1:] *= rescale_hw.flip(0)
+        q[:, :, 1:] = q[:, :, 1:].flip(-1)                        # (t, x, y) -> (t, y, x)
+        out = self._model(frames01, q)
+        dev = out["tracks"].device
+        occlusion = out["occlusion"].permute(0, 2, 1)
+        visibilities = (1 - torch.sigmoid(occlusion)) > self.visibility_threshold
+        trajectories = out["tracks"].permute(0, 2, 1, 3) / rescale_hw.flip(-1).to(dev)
+        return trajectories, visibilities
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # SuperGlue (sam_pt/point_tracker/superglue/)
 # ------------------------------------------------------------------------------------------------------------------
 SUPERPOINT_DEFAULTS = {"descriptor_dim": 256, "nms_radius": 4, "keypoint_threshold": 0.005, "max_keypoints": -1,

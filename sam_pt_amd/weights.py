@@ -17,7 +17,7 @@ from __future__ import annotations
 import math
 from collections import OrderedDict
 from dataclasses import dataclass, field
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -664,3 +664,140 @@ def tapir_state_dict_to_haiku(sd: Dict[str, torch.Tensor]) -> Dict[str, Dict[str
             a = a.reshape(a.shape[0], 1, a.shape[1])
         params.setdefault(module, {})[name] = a.contiguous().numpy()
     return params
+
+
+# --------------------------------------------------------------------------------------
+# TapNet (deepmind/tapnet @ ba1a8c8, vendored by the reference under sam_pt/point_tracker/tapnet)
+# --------------------------------------------------------------------------------------
+TAPNET_UNITS = ((64, 1, 0.125), (128, 2, 0.125), (256, 1, 0.0))     # channels, stride, shifted fraction of units 0 .. 2
+TAPNET_BN_EPS = 1e-5                                                # hk.BatchNorm's default
+
+
+def init_tapnet_state_dict(seed: int = 72, logit_gain: float = 0.5, occ_gain: float = 2000.0,
+                           occ_centre: float = 0.18545) -> "OrderedDict[str, torch.Tensor]":
+    """Random TapNet weights under flat names of this project's choosing, in PyTorch layouts (``load_tapnet_checkpoint`` maps a
+    Haiku checkpoint onto them):
+
+      tsm.stem.weight (64,3,7,7); tsm.u<U>.b<B>.{bn0,bn1}.{scale,offset,mean,var} — BatchNorm's parameters and its moving
+      statistics —, .{conv0,conv2}.weight (O,I,3,3) and, for B = 0, .shortcut.weight (O,I,1,1) — no convolution of the backbone has a
+      bias, and at depth 18 a block has no conv_1;
+      heads.{hid1,hid2,hid3}.{weight,bias} (O,I,3,3), heads.hid4.{weight,bias} (16,32), heads.occ_out.{weight,bias} (1,16).
+
+    CONDITIONED init, as for TAPIR.  The moving means and variances are drawn away from (0, 1), so the host's fold
+    into a per-channel affine is exercised.  ``hid1`` / ``hid2`` get a positive centre tap on top of their random weights and ``hid2``
+    the gain ``logit_gain``: the 10 x softmax then has one clear maximum near the best-correlated cell.  The occlusion head averages a
+    map over 256 cells, so with random weights its output barely moves between items (0.1850 .. 0.1859 on the golden clip):
+    ``occlusion_out`` is re-centred on ``occ_centre`` and scaled by ``occ_gain``, which spreads the logits over about +- 1, i.e. the
+    visibilities over both sides of the yaml's threshold 0.5."""
+    w = _Init(seed)
+    w.conv("tsm.stem", 64, 3, 7, 7, bias=False, kaiming_fan_out=True)
+    cin = 64
+    for u, (c, _, _) in enumerate(TAPNET_UNITS):
+        for b in range(2):
+            p = f"tsm.u{u}.b{b}"
+            bc = cin if b == 0 else c
+            for n, dim in (("bn0", bc), ("bn1", c)):
+                w.normal(f"{p}.{n}.scale", (dim,), 0.05, mean=1.0)
+                w.normal(f"{p}.{n}.offset", (dim,), 0.05)
+                w.normal(f"{p}.{n}.mean", (dim,), 0.2)
+                w.uniform(f"{p}.{n}.var", (dim,), 0.5)
+                w.sd[f"{p}.{n}.var"] += 1.25                      # in [0.75, 1.75]
+            w.conv(p + ".conv0", c, bc, 3, 3, bias=False, kaiming_fan_out=True)
+            w.conv(p + ".conv2", c, c, 3, 3, bias=False, kaiming_fan_out=True)
+            if b == 0:
+                w.conv(p + ".shortcut", c, bc, 1, 1, bias=False, kaiming_fan_out=True)
+        cin = c
+    w.conv("heads.hid1", 16, 1, 3, 3)
+    w.conv("heads.hid2", 1, 16, 3, 3)
+    w.conv("heads.hid3", 32, 16, 3, 3)
+    w.linear("heads.hid4", 16, 32)
+    w.linear("heads.occ_out", 1, 16)
+    w.sd["heads.hid1.weight"][:, 0, 1, 1] += 1.0
+    w.sd["heads.hid2.weight"][0, :, 1, 1] += 0.5
+    w.sd["heads.hid2.weight"] *= logit_gain
+    w.sd["heads.occ_out.weight"] *= occ_gain
+    w.sd["heads.occ_out.bias"] = (w.sd["heads.occ_out.bias"] - occ_centre) * occ_gain
+    return w.sd
+
+
+def tapnet_haiku_key_map() -> "OrderedDict[str, Tuple[str, str, str, str]]":
+    """our name -> (tree, Haiku module path, entry name, layout) for every tensor the forward pass uses; tree is "params" or "state".
+
+    UNVERIFIED AGAINST A REAL CHECKPOINT: no TapNet checkpoint exists where this project is built.  The paths are derived by reading
+    from Haiku's naming rules applied to tapnet_model.py and models/tsm_resnet.py: a module created in its parent's ``__init__`` is
+    ``parent/~/child``, one created inside another method is ``parent/child``; repeated names get ``_1``.  ``TAPNet`` names itself
+    ``tap_net`` (Haiku's snake case of the class name); the backbone (built in ``TAPNet.__init__``, name ``tsm_resnet_video``) and the
+    heads sit under ``tap_net/~/``; stem, units, blocks and their convolutions are built in ``__call__`` methods, so no ``~``; the two
+    ``hk.BatchNorm`` of a block, created through ``normalize_fn`` inside the block's ``__call__``, are ``batch_norm`` and
+    ``batch_norm_1``; the moving statistics are the ``average`` of the ExponentialMovingAverage children ``~/mean_ema`` / ``~/var_ema``
+    (built in ``BatchNorm.__init__``) in the state tree.  Layouts: conv2d = (kh, kw, cin, cout) -> (cout, cin, kh, kw); conv3d = the
+    heads' Conv3D (1, kh, kw, cin, cout) -> (cout, cin, kh, kw); linear = (in, out) -> (out, in); vec = unchanged; stat = (1, 1, 1, C) -> (C)."""
+    m: "OrderedDict[str, Tuple[str, str, str, str]]" = OrderedDict()
+    r = "tap_net/~/tsm_resnet_video/"
+    m["tsm.stem.weight"] = ("params", r + "tsm_resnet_stem", "w", "conv2d")
+    for u in range(3):
+        for b in range(2):
+            hp, p = f"{r}tsm_resnet_unit_{u}/block_{b}/", f"tsm.u{u}.b{b}."
+            for j, bn in enumerate(("batch_norm", "batch_norm_1")):
+                m[f"{p}bn{j}.scale"] = ("params", hp + bn, "scale", "stat")
+                m[f"{p}bn{j}.offset"] = ("params", hp + bn, "offset", "stat")
+                m[f"{p}bn{j}.mean"] = ("state", hp + bn + "/~/mean_ema", "average", "stat")
+                m[f"{p}bn{j}.var"] = ("state", hp + bn + "/~/var_ema", "average", "stat")
+            m[p + "conv0.weight"] = ("params", hp + "conv_0", "w", "conv2d")
+            m[p + "conv2.weight"] = ("params", hp + "conv_2", "w", "conv2d")
+            if b == 0:
+                m[p + "shortcut.weight"] = ("params", hp + "shortcut_conv", "w", "conv2d")
+    for ours, theirs, kind in (("hid1", "cost_volume_regression_1", "conv3d"), ("hid2", "cost_volume_regression_2", "conv3d"),
+                               ("hid3", "cost_volume_occlusion_1", "conv3d"), ("hid4", "cost_volume_occlusion_2", "linear"),
+                               ("occ_out", "occlusion_out", "linear")):
+        m[f"heads.{ours}.weight"] = ("params", "tap_net/~/" + theirs, "w", kind)
+        m[f"heads.{ours}.bias"] = ("params", "tap_net/~/" + theirs, "b", "vec")
+    return m
+
+
+def load_tapnet_checkpoint(path: str) -> "OrderedDict[str, torch.Tensor]":
+    """The reference's checkpoint format (tapnet/tracker.py:43-44): ``np.load(path, allow_pickle=True).item()`` of
+    ``checkpoint_wo_optstate.npy`` is ``{"params": {module path: {name: array}}, "state": {module path: {name: array}}}``.  -> a state
+    dict under this project's names and layouts (``tapnet_haiku_key_map``, UNVERIFIED AGAINST A REAL CHECKPOINT: none exists where
+    this project is built).  Modules the forward pass never calls (``regression_hid``, ``regression_out``, unit 3 of the backbone) and
+    the moving averages' ``hidden`` / ``counter`` are ignored; a tensor the map expects and the file lacks is named in the error."""
+    import numpy as np
+    ck = np.load(path, allow_pickle=True).item()
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    missing = []
+    for ours, (tree, module, name, kind) in tapnet_haiku_key_map().items():
+        src = ck[tree]
+        if module not in src or name not in src[module]:
+            missing.append(f"{tree}:{module}:{name}")
+            continue
+        a = torch.from_numpy(np.asarray(src[module][name], dtype=np.float32).copy())
+        if kind == "conv2d":
+            a = a.permute(3, 2, 0, 1)
+        elif kind == "conv3d":
+            a = a[0].permute(3, 2, 0, 1)
+        elif kind == "linear":
+            a = a.t()
+        elif kind == "stat":
+            a = a.reshape(-1)
+        sd[ours] = a.contiguous()
+    if missing:
+        raise KeyError(f"TapNet checkpoint {path} lacks {len(missing)} tensors: " + ", ".join(missing[:8]) + (" ..." if len(missing) > 8 else ""))
+    return sd
+
+
+def tapnet_state_dict_to_haiku(sd: Dict[str, torch.Tensor]) -> Dict[str, Dict[str, Dict[str, "object"]]]:
+    """The inverse of ``load_tapnet_checkpoint``'s mapping: ``{"params": ..., "state": ...}`` of a checkpoint file holding ``sd``
+    (round-trip tests)."""
+    ck: Dict[str, Dict[str, Dict[str, object]]] = {"params": {}, "state": {}}
+    for ours, (tree, module, name, kind) in tapnet_haiku_key_map().items():
+        a = sd[ours]
+        if kind == "conv2d":
+            a = a.permute(2, 3, 1, 0)
+        elif kind == "conv3d":
+            a = a.permute(2, 3, 1, 0)[None]
+        elif kind == "linear":
+            a = a.t()
+        elif kind == "stat":
+            a = a.reshape(1, 1, 1, -1)
+        ck[tree].setdefault(module, {})[name] = a.contiguous().numpy()
+    return ck
