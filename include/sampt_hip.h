@@ -481,6 +481,50 @@ int sampt_vit_encode_live(sampt_vit_t h, const uint8_t* frames_dev, int chw, int
                           size_t workspace_bytes, sampt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * seam 2a' — TinyViT image encoder = SamPredictor.set_image of MobileSAM and Light HQ-SAM (configs/model/sam/
+ * sam_mobile_vit_tiny.yaml, samhq_light_vit_tiny.yaml: Sam.preprocess + TinyViT of ChaoningZhang/MobileSAM tiny_vit_sam.py).
+ * Weight names: upstream's state-dict keys under `image_encoder.` after sam_pt_amd.pack.pack_tinyvit — every Conv2d_BN folded into
+ * `<conv>.weight` ([Cout][KH][KW][Cin], the stem's Cin zero-padded to 4; depthwise: [3][3][C]) and `<conv>.bias`, `.weight_hl`
+ * split-fp16 planes for the dense layers, `attn.attention_biases` [heads][ws^2], `attn.pad_qkv` [3 C] per block (the qkv of a
+ * zero-padded window position), the neck as for seam 2a (`neck.0.weight_hl`, `neck.2.weight_khwc_hl`).  One arithmetic, fp32
+ * grade.  embed_dims[i] / num_heads[i] must be 32 and window_sizes at most 14 for i >= 1; entry 0 of num_heads / window_sizes
+ * belongs to the convolutional stage and is not used.  PatchMerging strides follow upstream's rule: 1 where the merged width is
+ * 320, 448 or 576, else 2; the grid is img_size / 4 divided by those strides (img_size / 16 for every published model).
+ * encode: frames, chw, B <= max_batch, H, W, features_dev, workspace as for sampt_vit_encode (here H, W <= img_size is all that is
+ * asked); interm_out_dev: NULL, or float32 [B][grid*grid][embed_dims[2]] receiving the token map that enters layers.2 — Light
+ * HQ-SAM's interm_embeddings[0].  No host synchronisation.
+ * encode_stages (tests, measurement): additionally copies out the outputs of patch_embed and of layers 0..3, each after its
+ * downsample (stages_dev[5], NULL entries skipped; NHWC), and, with stage_ms (HOST float[6]) non-NULL, times patch_embed, the four
+ * layers and the neck with HIP events and synchronises with the stream before it returns. */
+typedef struct sampt_tinyvit* sampt_tinyvit_t;
+typedef struct sampt_tinyvit_config {
+  int img_size, out_chans, mlp_ratio, mbconv_expand_ratio;
+  int embed_dims[4], depths[4], num_heads[4], window_sizes[4];
+  float pixel_mean[3], pixel_std[3];
+} sampt_tinyvit_config;
+int sampt_tinyvit_create(const sampt_tinyvit_config* cfg, const char* const* names, const void* const* ptrs, int n, int max_batch,
+                         sampt_tinyvit_t* out);
+void sampt_tinyvit_destroy(sampt_tinyvit_t h);
+int sampt_tinyvit_encode_workspace_bytes(sampt_tinyvit_t h, int B, size_t* bytes);
+int sampt_tinyvit_encode(sampt_tinyvit_t h, const uint8_t* frames_dev, int chw, int B, int H, int W, float* features_dev,
+                         float* interm_out_dev, void* workspace_dev, size_t workspace_bytes, sampt_stream_t stream);
+int sampt_tinyvit_encode_stages(sampt_tinyvit_t h, const uint8_t* frames_dev, int chw, int B, int H, int W, float* features_dev,
+                                float* interm_out_dev, float* const stages_dev[5], float* stage_ms, void* workspace_dev,
+                                size_t workspace_bytes, sampt_stream_t stream);
+/* Kernel-level entry points (no handle; the kernels the engine launches, csrc/tinyvit.hip):
+ *   preprocess: uint8 frames (B,3,H,W) [chw] or (B,H,W,3) -> float32 [B][img][img][4] = (x - mean[c]) / std[c] inside the picture,
+ *     zeros outside it and in the 4th channel; mean / std: HOST float[3].
+ *   dwconv3x3: depthwise 3 x 3, pad 1, stride 1 or 2 over NHWC float32, weights [3][3][C], bias [C], optional erf-GELU; C % 32 == 0.
+ *   window_attention: qkv [B][H][W][96 heads] (per head q | k | v of 32), bias table [heads][ws^2] read at |dy| ws + |dx|, pad_qkv
+ *     [96 heads] = the qkv of a zero-padded position (padded keys take part in every softmax) -> out [B][H][W][32 heads]; ws <= 14. */
+int sampt_tinyvit_preprocess(const uint8_t* frames_dev, int chw, int B, int H, int W, int img_size, const float* mean, const float* std,
+                             float* out_dev, sampt_stream_t stream);
+int sampt_tinyvit_dwconv3x3_nhwc(const float* x_dev, const float* w_dev, const float* bias_dev, float* y_dev, int n, int H, int W, int C,
+                                 int stride, int gelu, sampt_stream_t stream);
+int sampt_tinyvit_window_attention_f32(const float* qkv_dev, const float* table_dev, const float* pad_qkv_dev, float* out_dev, int B,
+                                       int H, int W, int heads, int ws, sampt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * seam 2b — prompt encoder + mask decoder + postprocess = SamPredictor.predict_torch(multimask_output=False,
  * return_logits=True) as called at sam_pt.py:783-828.
  * --------------------------------------------------------------------------------------------------------- */

@@ -31,6 +31,12 @@ class VitConfigC(C.Structure):
                 ("global_mask", c_int), ("f16", c_int), ("pixel_mean", c_float * 3), ("pixel_std", c_float * 3)]
 
 
+class TinyVitConfigC(C.Structure):
+    _fields_ = [("img_size", c_int), ("out_chans", c_int), ("mlp_ratio", c_int), ("mbconv_expand_ratio", c_int),
+                ("embed_dims", c_int * 4), ("depths", c_int * 4), ("num_heads", c_int * 4), ("window_sizes", c_int * 4),
+                ("pixel_mean", c_float * 3), ("pixel_std", c_float * 3)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/sampt_hip.h
 _P = c_void_p
 _SIGS = {
@@ -119,6 +125,14 @@ _SIGS = {
     "sampt_attention_t2i_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
     "sampt_vit_live_rows": (c_int, [_P, c_int, c_int, C.POINTER(c_int), C.POINTER(c_size_t)]),
     "sampt_vit_encode_live": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, c_size_t, _P]),
+    "sampt_tinyvit_create": (c_int, [C.POINTER(TinyVitConfigC), C.POINTER(c_char_p), C.POINTER(_P), c_int, c_int, C.POINTER(_P)]),
+    "sampt_tinyvit_destroy": (None, [_P]),
+    "sampt_tinyvit_encode_workspace_bytes": (c_int, [_P, c_int, C.POINTER(c_size_t)]),
+    "sampt_tinyvit_encode": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "sampt_tinyvit_encode_stages": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, C.POINTER(_P), C.POINTER(c_float), _P, c_size_t, _P]),
+    "sampt_tinyvit_preprocess": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, C.POINTER(c_float), C.POINTER(c_float), _P, _P]),
+    "sampt_tinyvit_dwconv3x3_nhwc": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "sampt_tinyvit_window_attention_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "sampt_dec_create": (c_int, [C.POINTER(c_char_p), C.POINTER(_P), c_int, c_int, c_int, c_int, c_int, C.POINTER(_P)]),
     "sampt_dec_hq_workspace_bytes": (c_int, [_P, c_int, C.POINTER(c_size_t)]),
     "sampt_dec_hq_features": (c_int, [_P, c_int, _P, _P, _P, _P, c_size_t, _P]),

@@ -63,6 +63,7 @@ struct sampt_tapir {
 struct sampt_tapnet { TapnetEngine e; };
 struct sampt_sg { SgEngine e; };
 struct sampt_vit { VitEngine e; };
+struct sampt_tinyvit { TinyVitEngine e; };
 // hipGraph cache of the per-(frame, object) decode chain (north_star: "hipGraph capture of the per-frame decode"): one
 // instantiated graph per distinct call signature (every scalar AND every pointer of sampt_sam_track_decode_graph).
 struct DecGraphKey {
@@ -426,6 +427,74 @@ int sampt_vit_encode(sampt_vit_t h, const uint8_t* frames, int chw, int B, int H
                 "pipelines do)");
   Arena a(ws, ws_bytes);
   return h->e.encode(frames, chw, B, H, W, features, interm_out, a, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------- TinyViT
+int sampt_tinyvit_create(const sampt_tinyvit_config* cfg, const char* const* names, const void* const* ptrs, int n, int max_batch,
+                         sampt_tinyvit_t* out) {
+  if (!cfg || !names || !ptrs || !out || n < 1 || max_batch < 1) return fail(SAMPT_ERR_ARG, "sampt_tinyvit_create: bad arguments");
+  TinyVitConfig c;
+  c.img = cfg->img_size, c.out_chans = cfg->out_chans, c.mlp_ratio = cfg->mlp_ratio, c.expand = cfg->mbconv_expand_ratio;
+  for (int i = 0; i < 4; ++i)
+    c.dims[i] = cfg->embed_dims[i], c.depths[i] = cfg->depths[i], c.heads[i] = cfg->num_heads[i], c.windows[i] = cfg->window_sizes[i];
+  for (int i = 0; i < 3; ++i) c.mean[i] = cfg->pixel_mean[i], c.stdv[i] = cfg->pixel_std[i];
+  return create_handle<sampt_tinyvit>("sampt_tinyvit_create", out,
+                                      [&](sampt_tinyvit& h) { return h.e.init(make_map(names, ptrs, n), c, max_batch); });
+}
+void sampt_tinyvit_destroy(sampt_tinyvit_t h) { delete h; }
+
+int sampt_tinyvit_encode_workspace_bytes(sampt_tinyvit_t h, int B, size_t* bytes) {
+  if (!h || !bytes || B < 1) return fail(SAMPT_ERR_ARG, "sampt_tinyvit_encode_workspace_bytes: bad arguments");
+  Arena a(nullptr, 0);
+  int rc = h->e.encode(nullptr, 1, B, h->e.c.img, h->e.c.img, nullptr, nullptr, nullptr, nullptr, a, nullptr);
+  *bytes = a.peak + 256;
+  return rc == SAMPT_OK ? rc : fail(rc, "sampt_tinyvit_encode_workspace_bytes: " + h->e.error);
+}
+
+int sampt_tinyvit_encode_stages(sampt_tinyvit_t h, const uint8_t* frames, int chw, int B, int H, int W, float* features, float* interm_out,
+                                float* const stages[5], float* stage_ms, void* ws, size_t ws_bytes, sampt_stream_t stream) {
+  if (!h || !frames || !features || !ws || B < 1) return fail(SAMPT_ERR_ARG, "sampt_tinyvit_encode: bad arguments");
+  // the engine carves its scratch stage by stage between launches, so the size is checked before the first one
+  Arena dry(nullptr, 0);
+  int rc = h->e.encode(nullptr, chw, B, H, W, nullptr, nullptr, nullptr, nullptr, dry, nullptr);
+  if (rc != SAMPT_OK) return fail(rc, "sampt_tinyvit_encode: " + h->e.error);
+  if (dry.peak + 256 > ws_bytes) return fail(SAMPT_ERR_WORKSPACE, "sampt_tinyvit_encode: workspace too small (sampt_tinyvit_encode_workspace_bytes)");
+  Arena a(ws, ws_bytes);
+  if (!stage_ms) return h->e.encode(frames, chw, B, H, W, features, interm_out, stages, nullptr, a, (hipStream_t)stream);
+  hipEvent_t ev[7] = {};
+  rc = SAMPT_OK;
+  for (auto& e : ev)
+    if (hipEventCreate(&e) != hipSuccess) rc = SAMPT_ERR_HIP;
+  if (rc == SAMPT_OK) rc = h->e.encode(frames, chw, B, H, W, features, interm_out, stages, ev, a, (hipStream_t)stream);
+  if (rc == SAMPT_OK && hipEventSynchronize(ev[6]) != hipSuccess) rc = SAMPT_ERR_HIP;
+  for (int i = 0; i < 6 && rc == SAMPT_OK; ++i)
+    if (hipEventElapsedTime(&stage_ms[i], ev[i], ev[i + 1]) != hipSuccess) rc = SAMPT_ERR_HIP;
+  for (auto& e : ev)
+    if (e) (void)hipEventDestroy(e);
+  return rc;
+}
+
+int sampt_tinyvit_encode(sampt_tinyvit_t h, const uint8_t* frames, int chw, int B, int H, int W, float* features, float* interm_out,
+                         void* ws, size_t ws_bytes, sampt_stream_t stream) {
+  return sampt_tinyvit_encode_stages(h, frames, chw, B, H, W, features, interm_out, nullptr, nullptr, ws, ws_bytes, stream);
+}
+
+int sampt_tinyvit_preprocess(const uint8_t* frames, int chw, int B, int H, int W, int img_size, const float* mean, const float* std_,
+                             float* out, sampt_stream_t stream) {
+  int rc = tinyvit_preprocess(frames, chw, B, H, W, img_size, mean, std_, out, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_tinyvit_preprocess: bad arguments (H, W <= img_size)") : rc;
+}
+
+int sampt_tinyvit_dwconv3x3_nhwc(const float* x, const float* w, const float* bias, float* y, int n, int H, int W, int C, int stride, int gelu,
+                                 sampt_stream_t stream) {
+  int rc = tinyvit_dwconv3x3(x, w, bias, y, n, H, W, C, stride, gelu, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_tinyvit_dwconv3x3_nhwc: bad arguments (C % 32 == 0, stride 1 | 2, 16-byte aligned pointers)") : rc;
+}
+
+int sampt_tinyvit_window_attention_f32(const float* qkv, const float* table, const float* pad_qkv, float* out, int B, int H, int W, int heads,
+                                       int ws, sampt_stream_t stream) {
+  int rc = tinyvit_window_attention(qkv, table, pad_qkv, out, B, H, W, heads, ws, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_tinyvit_window_attention_f32: bad arguments (ws <= 14, 16-byte aligned pointers)") : rc;
 }
 
 // ------------------------------------------------------------------------------------------- PIPS++

@@ -302,6 +302,54 @@ struct VitEngine {
 };
 
 // -------------------------------------------------------------------------------------------------
+// TinyViT (MobileSAM / Light HQ-SAM image encoder; engine_tinyvit.hip).  Weights after sam_pt_amd.pack.pack_tinyvit: every BatchNorm
+// folded into its convolution, dense layers with split-fp16 planes, depthwise weights [3][3][C].  One arithmetic: fp32 grade.
+struct TinyVitConfig {
+  int img = 1024, out_chans = 256, mlp_ratio = 4, expand = 4;
+  int dims[4] = {64, 128, 160, 320}, depths[4] = {2, 2, 6, 2}, heads[4] = {2, 4, 5, 10}, windows[4] = {7, 7, 14, 7};
+  float mean[3] = {123.675f, 116.28f, 103.53f}, stdv[3] = {58.395f, 57.12f, 57.375f};
+};
+
+struct TinyVitEngine {
+  TinyVitConfig c;
+  struct DwW {
+    const float *w = nullptr, *b = nullptr;    // [3][3][C], [C]
+  };
+  struct MBConv {
+    ConvW conv1, conv3;
+    DwW conv2;
+  };
+  struct Merge {                               // PatchMerging: 1 x 1, depthwise 3 x 3 of stride `stride`, 1 x 1
+    ConvW conv1, conv3;
+    DwW conv2;
+    int stride = 2;
+  };
+  struct Blk {
+    const float *ln1w, *ln1b, *ln2w, *ln2b, *table, *pad_qkv;
+    ConvW qkv, proj, fc1, fc2;                 // the Linears as 1 x 1 convolutions over the token map
+    DwW local;
+  };
+  ConvW stem0, stem2;
+  std::vector<MBConv> mb;
+  Merge merge[3];
+  std::vector<Blk> blk[4];                     // [1..3] used
+  int res[4] = {0, 0, 0, 0};                   // side of the map layer i works on
+  const half_t *neck0_hl = nullptr, *neck2_hl = nullptr;
+  const float *neck0_w = nullptr, *neck2_w = nullptr, *neck1w, *neck1b, *neck3w, *neck3b;
+  int max_batch = 0;
+  std::string error;
+
+  int init(const WeightMap& w, const TinyVitConfig& cfg, int max_batch);
+  int grid() const { return res[3]; }
+  // frames: uint8 (B,3,H,W) if chw else (B,H,W,3), H, W <= img; features out [B][grid^2][out_chans] f32; interm_out (optional)
+  // [B][grid^2][dims[2]] = the token map that enters layers.2 (Light HQ-SAM's interm_embeddings[0]).  stages (optional, each entry
+  // optional): the outputs of patch_embed and of layers 0..3 (after their downsample), copied out for tests; stage_ev (optional): 7
+  // events recorded on s before patch_embed, after it, after each layer and after the neck.  No host synchronisation.
+  int encode(const uint8_t* frames, int chw, int B, int H, int W, float* features, float* interm_out, float* const* stages,
+             hipEvent_t* stage_ev, Arena& ws, hipStream_t s);
+};
+
+// -------------------------------------------------------------------------------------------------
 struct DecConfig {
   int grid = 64, C = 256, heads = 8, depth = 2, mlp = 2048, img = 1024;
   int vit_dim = 0;  // > 0: HQ-SAM decoder (MaskDecoderHQ) fed by a ViT of that width

@@ -158,6 +158,36 @@ inline Planes planes_for(Arena& ws, size_t elems, const ConvW& consumer) {
   return pl;
 }
 
+// SAM's neck (ImageEncoderViT.neck; the TinyViT encoder ends in the same one): conv1x1 (no bias) -> LayerNorm2d -> conv3x3, pad 1 (no
+// bias) -> LayerNorm2d over the token map x [B g g][D] -> features [B g g][C].  Each convolution has exact f32 weights (w0 [C][D],
+// w2 [C][3][3][C]) or, with those null, their split-fp16 planes (hl0, hl2): fp32 grade either way.  a, b: scratch [B g g][C] each.
+struct NeckW {
+  const void *w0 = nullptr, *w2 = nullptr;
+  const half_t *hl0 = nullptr, *hl2 = nullptr;
+  const float *n1w = nullptr, *n1b = nullptr, *n3w = nullptr, *n3b = nullptr;
+};
+inline int sam_neck(const NeckW& n, const float* x, int B, int g, int D, int C, float* a, float* b, float* features, hipStream_t s) {
+  const long Mg = (long)B * g * g;
+  GemmP p0 = gemm_linear(x, D, n.w0, nullptr, a, C, (int)Mg, C, D);
+  if (n.hl0) {
+    gemm_split_planes(p0, n.hl0);
+    SAMPT_TRY(conv_f16x3(p0, s));
+  } else {
+    SAMPT_TRY(gemm_f32(p0, s));
+  }
+  // (split-fp16 neck: the first LayerNorm2d writes its output as the two fp16 planes the halo-tiled 3 x 3 convolution stages by
+  //  LDS-DMA — same bytes as the f32 map in the same buffer, same hi / lo values the tiled kernel split on the fly, ~165 -> 110 us
+  //  per 8 frames (profiles/r6_c40_*); conv_halo_x3.hip)
+  const bool planes = n.hl2 && g_conv_halo && C % 256 == 0 && C <= 1536;
+  SAMPT_TRY(layernorm_rows(a, n.n1w, n.n1b, b, Mg, C, 1e-6f, nullptr, planes ? 3 : 0, ACT_NONE, s));
+  const ConvW neck2{(const float*)n.w2, nullptr, n.hl2, C, C, 3, 3, 1, 1, 1};
+  Planes xp;
+  if (planes) xp.hi = (half_t*)b, xp.lo = (half_t*)b + (size_t)Mg * C;
+  int oh, ow;
+  SAMPT_TRY(run_conv(neck2, b, B, g, g, a, 0, ACT_NONE, nullptr, oh, ow, false, s, xp));
+  return layernorm_rows(a, n.n3w, n.n3b, features, Mg, C, 1e-6f, nullptr, 0, ACT_NONE, s);
+}
+
 // One BasicEncoder residual block (extractor.py ResidualBlock) on cur [n][h][w][cin] (+ its planes); cur / cur_p / h / w become
 // the block's output.  next: the convolution that reads the output (null: none does), for its planes.
 //   instance: InstanceNorm after each convolution, the skip folded into the last instnorm_apply;

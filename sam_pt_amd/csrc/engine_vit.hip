@@ -273,22 +273,8 @@ int VitEngine::encode(const uint8_t* frames, int chw, int B, int H, int W, float
   if (dead_mode == 1) return SAMPT_ERR_ARG;   // (no global block: live_rows() already refused)
   // ---- neck: conv1x1 (no bias) -> LayerNorm2d -> conv3x3 (no bias) -> LayerNorm2d
   //      fp32 in both modes: the neck's operand roundings would land on the embedding undamped
-  SAMPT_TRY(gm.run(x, (int)Mg, D, neck0_w, nullptr, neck_a, c.out_chans, ACT_NONE, 0, nullptr, 0, nullptr, 0, nullptr,
-                   true, neck0_hl));
-  // (split-fp16 neck: the first LayerNorm2d writes its output as the two fp16 planes the halo-tiled 3 x 3 convolution stages by
-  //  LDS-DMA — same bytes as the f32 map in the same buffer, same hi / lo values the tiled kernel split on the fly, ~165 -> 110 us
-  //  per 8 frames (profiles/r6_c40_*); conv_halo_x3.hip)
-  const bool planes = neck2_hl && g_conv_halo && c.out_chans % 256 == 0 && c.out_chans <= 1536;
-  SAMPT_TRY(layernorm_rows(neck_a, neck1w, neck1b, neck_b, Mg, c.out_chans, 1e-6f, nullptr, planes ? 3 : 0, ACT_NONE, s));
-  {
-    const ConvW neck2{(const float*)neck2_w, nullptr, neck2_hl, c.out_chans, c.out_chans, 3, 3, 1, 1, 1};
-    Planes xp;
-    if (planes) xp.hi = (half_t*)neck_b, xp.lo = (half_t*)neck_b + (size_t)Mg * c.out_chans;
-    int oh, ow;
-    SAMPT_TRY(run_conv(neck2, neck_b, B, g, g, neck_a, 0, ACT_NONE, nullptr, oh, ow, false, s, xp));
-  }
-  SAMPT_TRY(layernorm_rows(neck_a, neck3w, neck3b, features, Mg, c.out_chans, 1e-6f, nullptr, 0, ACT_NONE, s));
-  return SAMPT_OK;
+  const NeckW nk{neck0_w, neck2_w, neck0_hl, neck2_hl, neck1w, neck1b, neck3w, neck3b};
+  return sam_neck(nk, x, B, g, D, c.out_chans, neck_a, neck_b, features, s);
 }
 
 }  // namespace sampt

@@ -256,6 +256,21 @@ int tapnet_query_feats(const float* grid, int T, const float* q, int n, float* q
 // cost-volume heads (cost_volume_heads.h: temperature 10, w5 [1][16], no ReLU after w3): qf [n][256]; pts [n T][2], occ [n T]
 int tapnet_heads(const float* grid, int T, const float* qf, const float* q, int n, const TapirHeadW& w, float* pts, float* occ, hipStream_t s);
 
+// ---- tinyvit.hip (TinyViT image encoder of MobileSAM / Light HQ-SAM; layouts in the file header) -----------------------------
+// Sam.preprocess for the convolutional stem: uint8 (B,3,H,W) [chw] or (B,H,W,3) -> f32 (B,img,img,4) = (x - mean) / std inside the
+// picture, zeros outside and in the 4th channel.  mean / stdv are HOST pointers (3 floats each)
+int tinyvit_preprocess(const uint8_t* frames, int chw, int B, int H, int W, int img, const float* mean, const float* stdv, float* dst,
+                       hipStream_t s);
+// depthwise 3 x 3, pad 1, stride 1 | 2: y [n][OH][OW][C] = (gelu)(conv(x [n][H][W][C], w [3][3][C]) + bias [C]); C % 32 == 0
+int tinyvit_dwconv3x3(const float* x, const float* w, const float* bias, float* y, int n, int H, int W, int C, int stride, int gelu,
+                      hipStream_t s);
+// window attention with a learned per-offset bias over ws x ws windows (ws <= 14, head width 32): qkv [B][H][W][3 * 32 heads] per-head
+// interleaved (q | k | v), table [heads][ws^2] read at |dy| ws + |dx|, pad_qkv [3 * 32 heads] = the qkv of a zero-padded position;
+// out [B][H][W][32 heads], real positions only
+int tinyvit_window_attention(const float* qkv, const float* table, const float* pad_qkv, float* out, int B, int H, int W, int heads, int ws,
+                             hipStream_t s);
+int tinyvit_gelu(const float* x, float* y, long n, hipStream_t s);      // y = erf-GELU(x), n % 4 == 0 (in place allowed)
+
 // ---- superglue.hip (SuperGlue point tracker, sam_pt/point_tracker/superglue/; layouts in the file header) --------------------
 // uint8 (T,3,H,W) -> f32 NHWC4 (T,H,W,4): channel 0 = uint8(0.2989 r + 0.587 g + 0.114 b) / 255, the rest zero
 int sg_grey(const uint8_t* frames, int T, int H, int W, float* dst, hipStream_t s);

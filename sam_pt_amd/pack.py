@@ -16,7 +16,7 @@ from typing import Dict
 
 import torch
 
-from .weights import SamConfig
+from .weights import SamConfig, TinyVitConfig
 
 
 def _khwc(w: torch.Tensor, pad_cin_to: int = 0) -> torch.Tensor:
@@ -512,6 +512,106 @@ def pack_vit(sd: Dict[str, torch.Tensor], cfg: SamConfig, device, f16, win_batch
         iv[r[v].long()] = v.to(torch.int32)
         out[f"__win_inv_live{k}"] = iv
         out[f"__win_pad_live{k}"] = (r < 0).nonzero().flatten().to(torch.int32)
+    return {k: v.to(device) for k, v in out.items()}
+
+
+def fold_conv_bn(sd: Dict[str, torch.Tensor], prefix: str, eps: float = 1e-5):
+    """TinyViT's ``Conv2d_BN`` (children ``c``: bias-free Conv2d, ``bn``: eval-mode BatchNorm2d) as one convolution, formed in
+    float64: w' = w * gamma / sqrt(var + eps) per output channel, b' = beta - mean * gamma / sqrt(var + eps)."""
+    g = sd[prefix + ".bn.weight"].double() / torch.sqrt(sd[prefix + ".bn.running_var"].double() + eps)
+    w = sd[prefix + ".c.weight"].double() * g.view(-1, 1, 1, 1)
+    b = sd[prefix + ".bn.bias"].double() - sd[prefix + ".bn.running_mean"].double() * g
+    return w.float(), b.float()
+
+
+def tinyvit_bias_index(ws: int) -> torch.Tensor:
+    """``attention_bias_idxs`` of a ws x ws window, (ws^2, ws^2): upstream numbers the offsets (|dy|, |dx|) by first appearance over
+    ``itertools.product(range(ws), range(ws))^2``, which is |dy| * ws + |dx| (tests/test_tinyvit_cpu.py holds the two equal)."""
+    y, x = torch.arange(ws).repeat_interleave(ws), torch.arange(ws).repeat(ws)
+    return (y[:, None] - y[None, :]).abs() * ws + (x[:, None] - x[None, :]).abs()
+
+
+def check_tinyvit_config(cfg: TinyVitConfig) -> None:
+    """What the TinyViT engine (csrc/engine_tinyvit.hip, csrc/tinyvit.hip) is built for; anything else is refused, naming the field."""
+    for i, d in enumerate(cfg.embed_dims):
+        if d % 32:
+            raise ValueError(f"pack_tinyvit: embed_dims[{i}] = {d} is not a multiple of 32")
+    for i in range(1, 4):
+        if cfg.embed_dims[i] != 32 * cfg.num_heads[i]:
+            raise ValueError(f"pack_tinyvit: num_heads[{i}] = {cfg.num_heads[i]} gives a head width of "
+                             f"{cfg.embed_dims[i] / cfg.num_heads[i]:g}; the window attention kernel is built for 32")
+        if not 1 <= cfg.window_sizes[i] <= 14:
+            raise ValueError(f"pack_tinyvit: window_sizes[{i}] = {cfg.window_sizes[i]} is outside 1 .. 14")
+    if cfg.local_conv_size != 3:
+        raise ValueError(f"pack_tinyvit: local_conv_size = {cfg.local_conv_size}; the depthwise kernel is 3 x 3")
+    if cfg.out_chans % 32:
+        raise ValueError(f"pack_tinyvit: out_chans = {cfg.out_chans} is not a multiple of 32")
+    r = cfg.img_size // 4
+    ok = cfg.img_size % 32 == 0
+    for st in cfg.merge_strides:
+        ok = ok and r % st == 0
+        r //= st
+    if not ok or r != cfg.grid:
+        raise ValueError(f"pack_tinyvit: img_size = {cfg.img_size} does not divide down the stages to the {cfg.grid} x {cfg.grid} grid "
+                         f"(img_size / patch_size): resolutions {cfg.resolutions}")
+
+
+def pack_tinyvit(sd: Dict[str, torch.Tensor], cfg: TinyVitConfig, device) -> Dict[str, torch.Tensor]:
+    """TinyViT (csrc/engine_tinyvit.hip) from upstream's keys under ``image_encoder.``: every ``Conv2d_BN`` folded (``fold_conv_bn``)
+    into ``<conv>.weight`` / ``<conv>.bias`` — dense convolutions [Cout][KH][KW][Cin] (the stem's Cin zero-padded 3 -> 4), depthwise
+    ones [3][3][C]; the Linears as they are; ``.weight_hl`` split-fp16 planes for every dense layer whose Cin is a multiple of 32
+    (all but the stem); per block ``attn.pad_qkv`` = W_qkv beta + b_qkv, the qkv of a zero-padded window position (LayerNorm of a
+    zero token is its bias beta), formed in float64; the bias tables as they are; the neck as ``pack_vit`` packs it for its 16-bit
+    modes.  ``norm_head``, ``head``, ``num_batches_tracked`` and ``attention_bias_idxs`` are ignored."""
+    check_tinyvit_config(cfg)
+    e = "image_encoder."
+    out: Dict[str, torch.Tensor] = {}
+
+    def dense(name, w, b):                      # w: [Cout][Cin][KH][KW] or [N][K]
+        w = w.float()
+        cin = w.shape[1]
+        wk = _khwc(w, 4 if cin == 3 else 0) if w.dim() == 4 else w.contiguous()
+        out[name + ".weight"], out[name + ".bias"] = wk, b.float().contiguous()
+        if cin % 32 == 0:
+            _put_split(out, name + ".weight_hl", wk)
+
+    def depthwise(name, w, b):                  # w: [C][1][3][3] -> [3][3][C]
+        out[name + ".weight"] = w.float()[:, 0].permute(1, 2, 0).contiguous()
+        out[name + ".bias"] = b.float().contiguous()
+
+    def conv_bn(name, dw=False):
+        (depthwise if dw else dense)(name, *fold_conv_bn(sd, name))
+
+    def merging(p):
+        conv_bn(p + ".conv1"), conv_bn(p + ".conv2", dw=True), conv_bn(p + ".conv3")
+
+    conv_bn(e + "patch_embed.seq.0"), conv_bn(e + "patch_embed.seq.2")
+    for b in range(cfg.depths[0]):
+        merging(f"{e}layers.0.blocks.{b}")
+    for i in range(3):
+        merging(f"{e}layers.{i}.downsample")
+    for i in range(1, 4):
+        ws = cfg.window_sizes[i]
+        for b in range(cfg.depths[i]):
+            p = f"{e}layers.{i}.blocks.{b}"
+            for lin in (".attn.qkv", ".attn.proj", ".mlp.fc1", ".mlp.fc2"):
+                dense(p + lin, sd[p + lin + ".weight"], sd[p + lin + ".bias"])
+            for nm in (".attn.norm", ".mlp.norm"):
+                out[p + nm + ".weight"] = sd[p + nm + ".weight"].float().contiguous()
+                out[p + nm + ".bias"] = sd[p + nm + ".bias"].float().contiguous()
+            tab = sd[p + ".attn.attention_biases"].float().contiguous()
+            if tuple(tab.shape) != (cfg.num_heads[i], ws * ws):
+                raise ValueError(f"pack_tinyvit: {p}.attn.attention_biases is {tuple(tab.shape)}, window_sizes[{i}] = {ws} and "
+                                 f"num_heads[{i}] = {cfg.num_heads[i]} ask for {(cfg.num_heads[i], ws * ws)}")
+            out[p + ".attn.attention_biases"] = tab
+            out[p + ".attn.pad_qkv"] = (sd[p + ".attn.qkv.weight"].double() @ sd[p + ".attn.norm.bias"].double()
+                                        + sd[p + ".attn.qkv.bias"].double()).float().contiguous()
+            conv_bn(p + ".local_conv", dw=True)
+    n0 = sd[e + "neck.0.weight"].float()
+    out[e + "neck.0.weight_hl"] = split_f16x3(n0.reshape(n0.shape[0], -1).contiguous())
+    out[e + "neck.2.weight_khwc_hl"] = split_f16x3(_khwc(sd[e + "neck.2.weight"].float()))
+    for k in ("neck.1.weight", "neck.1.bias", "neck.3.weight", "neck.3.bias"):
+        out[e + k] = sd[e + k].float().contiguous()
     return {k: v.to(device) for k, v in out.items()}
 
 

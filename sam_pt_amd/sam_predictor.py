@@ -23,8 +23,8 @@ import torch
 from torch import nn
 
 from . import _lib
-from .pack import VIT_GEMM_KINDS, pack_decoder, pack_vit, vit_bias_correction
-from .weights import SAM_CONFIGS, SamConfig, init_sam_state_dict
+from .pack import VIT_GEMM_KINDS, pack_decoder, pack_tinyvit, pack_vit, vit_bias_correction
+from .weights import SAM_CONFIGS, SamConfig, TinyVitConfig, init_sam_state_dict
 
 
 def pil_bilinear_tables(in_size: int, out_size: int):
@@ -150,7 +150,7 @@ class SamHip(nn.Module):
     def __init__(self, variant: Optional[str] = None, checkpoint: Optional[str] = None, state_dict=None, seed: int = 72,
                  precision: str = "f16", config: Optional[SamConfig] = None, max_batch: int = 8,
                  max_decode_batch: int = 128, hq: Optional[bool] = None, image_encoder=None, prompt_encoder=None,
-                 mask_decoder=None, pixel_mean=None, pixel_std=None, **hydra_kwargs):
+                 mask_decoder=None, pixel_mean=None, pixel_std=None, clip_decode_batch: Optional[int] = None, **hydra_kwargs):
         """``hq``: build the HQ-SAM decoder (sam_pt/modeling/sam.py SamHQHydra, configs/model/sam/samhq_vit_*.yaml);
         default: inferred from the checkpoint (presence of ``mask_decoder.hf_token.weight``) or from the ``mask_decoder``
         node's ``_target_`` (``...MaskDecoderHQ``).
@@ -161,14 +161,26 @@ class SamHip(nn.Module):
         the node is left un-instantiated (``+...sam_model._recursive_=false``), or upstream's
         ``ImageEncoderViT`` object if Hydra did instantiate it; ``variant`` is only a shorthand for code that builds the
         object by hand.  ``prompt_encoder`` / ``mask_decoder`` hyper-parameters are the fixed ones of
-        configs/model/sam/{prompt_encoder,mask_decoder}/sam.yaml and are checked, not used."""
+        configs/model/sam/{prompt_encoder,mask_decoder}/sam.yaml and are checked, not used.
+
+        TinyViT (MobileSAM, Light HQ-SAM: configs/model/sam/sam_mobile_vit_tiny.yaml, samhq_light_vit_tiny.yaml; by hand
+        ``variant="vit_t"``): an ``image_encoder`` node with ``embed_dims`` (or a ``_target_`` ending in ``TinyViT``, or upstream's
+        ``TinyViT`` object) gives a ``TinyVitConfig``.  That encoder has ONE arithmetic, fp32 grade (split-fp16 products for the
+        dense layers, f32 FMAs in its depthwise convolutions and window attention): ``precision`` is accepted with all three
+        values and has no effect on it.  Its checkpoint key map is restated from upstream's module tree and UNVERIFIED against
+        a real ``mobile_sam.pt`` / ``sam_hq_vit_tiny.pth``; parity with upstream is unpinned (tests/tinyvit_ref.py).
+
+        ``clip_decode_batch``: items per decoder chain of ``SamPt``'s fused clip path.  None leaves it at ``max_decode_batch`` for a
+        ViT encoder and makes it 1 for a TinyViT one: the decoder's f32 GEMMs choose their kernel by row count, so only a chain of
+        one item sums in the order of a ``predict_torch`` call, and this encoder's clip path is held to the per-frame path bit for
+        bit.  A larger value batches the chains again, at a difference of a few 1e-7 in the logits."""
         super().__init__()
         if config is None:
             config = self._config_from_hydra(image_encoder, mask_decoder, pixel_mean, pixel_std, hydra_kwargs)
         if config is None:
             config = SAM_CONFIGS[variant if variant is not None else "vit_h"]
-        elif variant is not None and (SAM_CONFIGS[variant].embed_dim, SAM_CONFIGS[variant].depth) != (config.embed_dim, config.depth):
-            raise ValueError(f"variant={variant} contradicts the image_encoder config (embed_dim {config.embed_dim}, depth {config.depth})")
+        elif variant is not None and self._geometry(SAM_CONFIGS[variant]) != self._geometry(config):
+            raise ValueError(f"variant={variant} contradicts the image_encoder config {self._geometry(config)}")
         self.cfg = config
         if hq is None and mask_decoder is not None:
             tgt = mask_decoder.get("_target_", "") if hasattr(mask_decoder, "get") else type(mask_decoder).__name__
@@ -190,6 +202,11 @@ class SamHip(nn.Module):
         self.precision = precision
         self.max_batch = max_batch
         self.max_decode_batch = max_decode_batch
+        if clip_decode_batch is None and isinstance(self.cfg, TinyVitConfig):
+            clip_decode_batch = 1
+        if clip_decode_batch is not None and not 1 <= int(clip_decode_batch) <= max_decode_batch:
+            raise ValueError(f"clip_decode_batch={clip_decode_batch} must lie in 1..max_decode_batch ({max_decode_batch})")
+        self.clip_decode_batch = clip_decode_batch          # None: SamPt chunks its clip chains by max_decode_batch
         self.register_buffer("pixel_mean", torch.tensor(self.cfg.pixel_mean).view(-1, 1, 1), persistent=False)
         self.prompt_embed_dim, self.image_size = self.cfg.out_chans, self.cfg.img_size
         self.vit_patch_size, self.image_embedding_size = self.cfg.patch_size, self.cfg.grid
@@ -201,11 +218,60 @@ class SamHip(nn.Module):
         return self._sd
 
     @staticmethod
-    def _config_from_hydra(image_encoder, mask_decoder, pixel_mean, pixel_std, kw) -> Optional[SamConfig]:
-        """SamConfig from the keyword arguments Hydra passes for configs/model/sam/*.yaml (None if there is no
+    def _geometry(cfg):
+        if isinstance(cfg, TinyVitConfig):
+            return ("TinyViT", tuple(cfg.embed_dims), tuple(cfg.depths))
+        return ("ViT", cfg.embed_dim, cfg.depth)
+
+    @staticmethod
+    def _tinyvit_from_hydra(image_encoder, pixel_mean, pixel_std, kw) -> Optional[TinyVitConfig]:
+        """TinyVitConfig when the ``image_encoder`` node is a TinyViT — a mapping with ``embed_dims`` or a ``_target_`` ending in
+        ``TinyViT``, or an instantiated object with ``layers`` and ``patch_embed.seq`` — else None."""
+        four = lambda v: tuple(int(x) for x in v)
+        if hasattr(image_encoder, "get"):
+            ie = image_encoder
+            if ie.get("embed_dims", None) is None and not str(ie.get("_target_", "")).endswith("TinyViT"):
+                return None
+            d = SAM_CONFIGS["vit_t"]
+            fields = dict(embed_dims=four(ie.get("embed_dims", d.embed_dims)), depths=four(ie.get("depths", d.depths)),
+                          num_heads=four(ie.get("num_heads", d.num_heads)), window_sizes=four(ie.get("window_sizes", d.window_sizes)),
+                          img_size=int(ie.get("img_size", kw.get("image_size", 1024))), mlp_ratio=int(ie.get("mlp_ratio", 4)),
+                          mbconv_expand_ratio=int(ie.get("mbconv_expand_ratio", 4)), local_conv_size=int(ie.get("local_conv_size", 3)))
+        elif hasattr(image_encoder, "layers") and hasattr(getattr(image_encoder, "patch_embed", None), "seq"):
+            layers = list(image_encoder.layers)
+            seq = image_encoder.patch_embed.seq
+            dims = [int(seq[2].c.out_channels)] + [int(l.blocks[0].attn.norm.normalized_shape[0]) for l in layers[1:]]
+            fields = dict(embed_dims=tuple(dims), depths=tuple(len(l.blocks) for l in layers),
+                          num_heads=(dims[0] // 32,) + tuple(int(l.blocks[0].attn.attention_biases.shape[0]) for l in layers[1:]),
+                          window_sizes=(7,) + tuple(int(round(l.blocks[0].attn.attention_biases.shape[1] ** 0.5)) for l in layers[1:]),
+                          img_size=int(image_encoder.img_size),
+                          mlp_ratio=int(layers[1].blocks[0].mlp.fc1.out_features // dims[1]),
+                          mbconv_expand_ratio=int(layers[0].blocks[0].conv1.c.out_channels // dims[0]),
+                          local_conv_size=int(layers[1].blocks[0].local_conv.c.kernel_size[0]))
+        else:
+            return None
+        if pixel_mean is not None:
+            fields["pixel_mean"] = tuple(float(v) for v in pixel_mean)
+        if pixel_std is not None:
+            fields["pixel_std"] = tuple(float(v) for v in pixel_std)
+        fields["out_chans"] = int(kw.get("prompt_embed_dim", 256))
+        if "vit_patch_size" in kw and int(kw["vit_patch_size"]) != 16:
+            raise ValueError("SamHip: a TinyViT encoder has a total stride of 16 (vit_patch_size)")
+        if "image_embedding_size" in kw and int(kw["image_embedding_size"]) != fields["img_size"] // 16:
+            raise ValueError("image_embedding_size must equal image_size / vit_patch_size")
+        name = "vit_t" if (fields["embed_dims"], fields["depths"]) == (SAM_CONFIGS["vit_t"].embed_dims, SAM_CONFIGS["vit_t"].depths) \
+            else "vit_t_" + "x".join(str(v) for v in fields["embed_dims"])
+        return TinyVitConfig(name, **fields)
+
+    @staticmethod
+    def _config_from_hydra(image_encoder, mask_decoder, pixel_mean, pixel_std, kw):
+        """SamConfig (or TinyVitConfig) from the keyword arguments Hydra passes for configs/model/sam/*.yaml (None if there is no
         ``image_encoder`` node to read)."""
         if image_encoder is None:
             return None
+        tiny = SamHip._tinyvit_from_hydra(image_encoder, pixel_mean, pixel_std, kw)
+        if tiny is not None:
+            return tiny
         if hasattr(image_encoder, "get"):                                   # un-instantiated node (mapping / DictConfig)
             ie = image_encoder
             g = lambda k, d=None: ie.get(k, d)
@@ -250,6 +316,10 @@ class SamPredictor(_lib.EngineOwner):
     def __init__(self, sam_model: SamHip):
         self.model = sam_model
         self.transform = ResizeLongestSide(sam_model.cfg.img_size)
+        # a TinyViT encoder (MobileSAM, Light HQ-SAM) lives behind its own engine; the handle keeps the name ``_vit``
+        self._tiny = isinstance(sam_model.cfg, TinyVitConfig)
+        if self._tiny:
+            self._engines = (("_vit", "sampt_tinyvit_destroy"), ("_dec", "sampt_dec_destroy"))
         self._vit = self._dec = None
         self._dev = None
         self._ws_vit: Dict[int, torch.Tensor] = {}
@@ -261,11 +331,11 @@ class SamPredictor(_lib.EngineOwner):
         # hipGraph replay of the per-(frame, object) decode chain (sampt_sam_track_decode_graph); SAMPT_DEC_GRAPH=0|1
         self.use_graph = os.environ.get("SAMPT_DEC_GRAPH", "1") != "0"
         # skip the frame-independent padding rows of landscape frames in the blocks before the first global one (exact)
-        self.skip_dead_rows = os.environ.get("SAMPT_VIT_SKIP_DEAD", "1") != "0"
+        self.skip_dead_rows = os.environ.get("SAMPT_VIT_SKIP_DEAD", "1") != "0" and not self._tiny
         self._dead_cache = {}
         # fp16 ViT mode: static bias correction of the weight rounding, calibrated once per frame geometry (see
         # ``_select_bias_set``); SAMPT_VIT_BIAS_CORR=0 disables
-        self.bias_correction = os.environ.get("SAMPT_VIT_BIAS_CORR", "1") != "0"
+        self.bias_correction = os.environ.get("SAMPT_VIT_BIAS_CORR", "1") != "0" and not self._tiny
         self._bias_orig: Optional[Dict[str, torch.Tensor]] = None
         self._bias_sets: Dict[Tuple[int, int], Dict[str, torch.Tensor]] = {}
         self._bias_live = None
@@ -297,7 +367,29 @@ class SamPredictor(_lib.EngineOwner):
         self._bias_sets.clear()
         self.reset_image()
 
+    def _vit_only(self, what: str):
+        """The ViT engine's machinery has no counterpart in the TinyViT engine: asked for there, it is refused by name."""
+        if self._tiny:
+            raise _lib.SamptError(f"SamPredictor.{what}: ImageEncoderViT only; the TinyViT encoder ({self.model.cfg.name}) has none")
+
+    def _build_tinyvit(self, lib, dev):
+        cfg, m = self.model.cfg, self.model
+        self._wv = pack_tinyvit(m.sd, cfg, dev)
+        c = _lib.TinyVitConfigC()
+        c.img_size, c.out_chans, c.mlp_ratio, c.mbconv_expand_ratio = cfg.img_size, cfg.out_chans, cfg.mlp_ratio, cfg.mbconv_expand_ratio
+        for i in range(4):
+            c.embed_dims[i], c.depths[i], c.num_heads[i], c.window_sizes[i] = (cfg.embed_dims[i], cfg.depths[i], cfg.num_heads[i],
+                                                                                cfg.window_sizes[i])
+        for i in range(3):
+            c.pixel_mean[i], c.pixel_std[i] = cfg.pixel_mean[i], cfg.pixel_std[i]
+        self._vit = _lib.create_engine(lib, "sampt_tinyvit_create", self._wv, m.max_batch, pre=(C.byref(c),))
+        self._wd = pack_decoder(m.sd, cfg, dev, m.max_decode_batch, hq=m.hq)
+        return self._vit, _lib.create_engine(lib, "sampt_dec_create", self._wd, cfg.grid, cfg.img_size, m.max_decode_batch,
+                                             cfg.hq_dim if m.hq else 0)
+
     def _build(self, lib, dev):
+        if self._tiny:
+            return self._build_tinyvit(lib, dev)
         cfg, m = self.model.cfg, self.model
         f16 = {"f32": 0, "f16": 1, "f16x3": 2}[m.precision]
         self._wv = pack_vit(m.sd, cfg, dev, f16, m.max_batch)
@@ -312,13 +404,14 @@ class SamPredictor(_lib.EngineOwner):
         self._vit = _lib.create_engine(lib, "sampt_vit_create", self._wv, m.max_batch, pre=(C.byref(c),))
         self._wd = pack_decoder(m.sd, cfg, dev, m.max_decode_batch, hq=m.hq)
         return self._vit, _lib.create_engine(lib, "sampt_dec_create", self._wd, cfg.grid, cfg.img_size, m.max_decode_batch,
-                                             cfg.embed_dim if m.hq else 0)
+                                             cfg.hq_dim if m.hq else 0)
 
     @_lib.on_device(lambda self, *a, **k: self.model.device)
     def set_gemm_workgroups(self, per_xcd):
         """Persistent GEMM workgroups per XCD (of 32 CUs) for the following ``encode_frames`` calls; 0 = one per CU.  An int, or
         four ints (qkv, proj, fc1, fc2): one count per launch kind.  See sampt_vit_set_gemm_workgroups(_kind)
         (include/sampt_hip.h)."""
+        self._vit_only("set_gemm_workgroups")
         self._ensure()
         if isinstance(per_xcd, (tuple, list)):
             q, p, f1, f2 = (int(v) for v in per_xcd)
@@ -330,12 +423,14 @@ class SamPredictor(_lib.EngineOwner):
     @_lib.on_device(lambda self, *a, **k: self.model.device)
     def gemm_profile_begin(self):
         """Start timing every fp16 GEMM launch of the image encoder with HIP events (see sampt_vit_profile_begin)."""
+        self._vit_only("gemm_profile_begin")
         self._ensure()
         _lib.check(self._lib.sampt_vit_profile_begin(self._vit), "sampt_vit_profile_begin")
 
     @_lib.on_device(lambda self, *a, **k: self.model.device)
     def gemm_profile_end(self):
         """-> (algorithmic FLOP, kernel milliseconds, launches) since gemm_profile_begin."""
+        self._vit_only("gemm_profile_end")
         fl, ms, n = C.c_double(), C.c_double(), C.c_int()
         _lib.check(self._lib.sampt_vit_profile_end(self._vit, C.byref(fl), C.byref(ms), C.byref(n)), "sampt_vit_profile_end")
         return fl.value, ms.value, n.value
@@ -355,6 +450,10 @@ class SamPredictor(_lib.EngineOwner):
         error; the attention kernels read it from the separate fp16 bias row).  Deterministic: the same geometry always gets
         the same biases, whatever was encoded before."""
         m = self.model
+        if self._tiny:
+            if self.bias_correction:
+                self._vit_only("bias_correction")
+            return
         if not self.bias_correction or m.precision != "f16":
             if self._bias_live is not None:       # switched off at run time: the original biases come back, and with them go
                 for k, v in self._bias_orig.items():      # the dead rows that were computed under the corrected ones
@@ -400,13 +499,15 @@ class SamPredictor(_lib.EngineOwner):
 
     def _vit_ws(self, B: int) -> torch.Tensor:
         if B not in self._ws_vit:
-            self._ws_vit = {B: _lib.workspace("sampt_vit_encode_workspace_bytes", self._dev, self._vit, B)}  # only the latest size
+            query = "sampt_tinyvit_encode_workspace_bytes" if self._tiny else "sampt_vit_encode_workspace_bytes"
+            self._ws_vit = {B: _lib.workspace(query, self._dev, self._vit, B)}  # only the latest size
         return self._ws_vit[B]
 
     def _dead_rows(self, frames: torch.Tensor, chw: bool, H: int, W: int, ws: torch.Tensor) -> Optional[torch.Tensor]:
         """Residual stream of the token rows no pixel of an (H, W) frame reaches (the zero padding of Sam.preprocess below
         a landscape frame) at the input of the first global-attention block: the same in every frame, computed once per
         geometry from the first frame that has it (sampt_vit_encode_live, include/sampt_hip.h).  None: nothing to skip."""
+        self._vit_only("skip_dead_rows")
         key = (H, W)      # (an entry is always computed under its geometry's bias set: _select_bias_set drops it on a toggle)
         if key not in self._dead_cache:
             lh, nb = C.c_int(), C.c_size_t()
@@ -446,7 +547,8 @@ class SamPredictor(_lib.EngineOwner):
         current stream when frames [.., end_frame) are done — lets a caller start decoding early frames on another stream
         while later batches are still being encoded.  ``gemm_workgroups``: persistent GEMM workgroups per XCD for the encoder
         batches of this call — an int, or a sequence with one entry per batch (the last one repeats); see
-        ``set_gemm_workgroups``.  Reset to the default (one per CU) afterwards."""
+        ``set_gemm_workgroups``.  Reset to the default (one per CU) afterwards.  (A hint to the ViT's persistent GEMMs: the TinyViT
+        encoder has none and ignores it.)"""
         self._ensure()
         frames = frames.to(self._dev).contiguous()
         frames = self.transform.apply_image_torch(frames, chw=chw)      # PIL-exact resize when the longest side != img_size
@@ -458,11 +560,11 @@ class SamPredictor(_lib.EngineOwner):
         hq = interm = None
         if self.model.hq:
             hq = torch.empty((T, 16 * g * g, Cc // 8), dtype=torch.float32, device=self._dev)
-            interm = torch.empty((min(Bm, T), g * g, self.model.cfg.embed_dim), dtype=torch.float32, device=self._dev)
+            interm = torch.empty((min(Bm, T), g * g, self.model.cfg.hq_dim), dtype=torch.float32, device=self._dev)
         self._select_bias_set(H, W)
         dead = self._dead_rows(frames, chw, H, W, self._vit_ws(min(Bm, T))) if self.skip_dead_rows else None
         # one entry per batch (the last repeats); an entry is an int or a (qkv, proj, fc1, fc2) tuple
-        wgs = None if gemm_workgroups is None else ([int(gemm_workgroups)] if isinstance(gemm_workgroups, int)
+        wgs = None if gemm_workgroups is None or self._tiny else ([int(gemm_workgroups)] if isinstance(gemm_workgroups, int)
                                                       else [tuple(int(x) for x in v) if isinstance(v, (tuple, list)) else int(v)
                                                             for v in gemm_workgroups])
         for bi, t0 in enumerate(range(0, T, Bm)):
@@ -470,7 +572,11 @@ class SamPredictor(_lib.EngineOwner):
             ws = self._vit_ws(B)
             if wgs:
                 self.set_gemm_workgroups(wgs[min(bi, len(wgs) - 1)])
-            if dead is not None:
+            if self._tiny:
+                _lib.check(self._lib.sampt_tinyvit_encode(self._vit, _lib.ptr(frames[t0:t0 + B]), 1 if chw else 0, B, H, W,
+                                                          _lib.ptr(out[t0:t0 + B]), _lib.ptr(interm), _lib.ptr(ws), ws.numel(),
+                                                          _lib.stream_ptr()), "sampt_tinyvit_encode")
+            elif dead is not None:
                 _lib.check(self._lib.sampt_vit_encode_live(self._vit, _lib.ptr(frames[t0:t0 + B]), 1 if chw else 0, B, H, W,
                                                            _lib.ptr(out[t0:t0 + B]), _lib.ptr(interm), _lib.ptr(dead), 0,
                                                            _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),

@@ -702,7 +702,8 @@ class SamPt(nn.Module):
         k_all = np.array([len(c) for c, _ in prompts], dtype=np.int32)
         npos_all = np.array([int((l == 1).sum()) for _, l in prompts], dtype=np.int32)
         two_pass = self.negative_points_per_mask > 0
-        Fmax = getattr(pred.model, "max_decode_batch", 1)
+        # (a TinyViT predictor asks for chains of one item, SamHip.clip_decode_batch: its clip path equals predict_torch bit for bit)
+        Fmax = getattr(pred.model, "clip_decode_batch", None) or getattr(pred.model, "max_decode_batch", 1)
         chunks = []                                                               # [(items, event to wait for or None)]
         if batch_events:
             lo = 0

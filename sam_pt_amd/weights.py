@@ -317,6 +317,61 @@ class SamConfig:
     def head_dim(self) -> int:
         return self.embed_dim // self.num_heads
 
+    @property
+    def hq_dim(self) -> int:
+        """Width of the token map HQ-SAM's decoder taps (``MaskDecoderHQ(vit_dim=...)``)."""
+        return self.embed_dim
+
+
+@dataclass(frozen=True)
+class TinyVitConfig:
+    """Hyper-parameters of a SAM whose image encoder is TinyViT (ChaoningZhang/MobileSAM tiny_vit_sam.py): MobileSAM
+    (configs/model/sam/sam_mobile_vit_tiny.yaml) and Light HQ-SAM (samhq_light_vit_tiny.yaml).  Entry 0 of ``num_heads`` /
+    ``window_sizes`` belongs to the convolutional stage and is unused, as upstream.  The prompt encoder / mask decoder fields are
+    ``SamConfig``'s; ``patch_size`` is the encoder's total stride (patch embed 4, two stride-2 PatchMergings)."""
+    name: str
+    embed_dims: Tuple[int, int, int, int]
+    depths: Tuple[int, int, int, int]
+    num_heads: Tuple[int, int, int, int]
+    window_sizes: Tuple[int, int, int, int]
+    img_size: int = 1024
+    patch_size: int = 16
+    mlp_ratio: int = 4
+    mbconv_expand_ratio: int = 4
+    local_conv_size: int = 3
+    out_chans: int = 256
+    mask_in_chans: int = 16
+    dec_depth: int = 2
+    dec_heads: int = 8
+    dec_mlp_dim: int = 2048
+    num_multimask_outputs: int = 3
+    iou_head_depth: int = 3
+    iou_head_hidden_dim: int = 256
+    pixel_mean: Tuple[float, float, float] = (123.675, 116.28, 103.53)
+    pixel_std: Tuple[float, float, float] = (58.395, 57.12, 57.375)
+
+    @property
+    def grid(self) -> int:
+        return self.img_size // self.patch_size
+
+    @property
+    def merge_strides(self) -> Tuple[int, int, int]:
+        """Stride of the PatchMerging after layers 0..2: upstream's rule is by VALUE of the merged width."""
+        return tuple(1 if d in (320, 448, 576) else 2 for d in self.embed_dims[1:])
+
+    @property
+    def resolutions(self) -> Tuple[int, int, int, int]:
+        """Side of the map each layer works on (img/4, then divided by the merge strides)."""
+        r = [self.img_size // 4]
+        for st in self.merge_strides:
+            r.append(r[-1] // st)
+        return tuple(r)
+
+    @property
+    def hq_dim(self) -> int:
+        """Width of the token map Light HQ-SAM's decoder taps: the input of ``layers.2``."""
+        return self.embed_dims[2]
+
 
 SAM_CONFIGS: Dict[str, SamConfig] = {
     "vit_b": SamConfig("vit_b", 768, 12, 12, (2, 5, 8, 11)),
@@ -325,16 +380,17 @@ SAM_CONFIGS: Dict[str, SamConfig] = {
     # reduced geometry for fast CPU tests only (same code paths: windows, padding, global blocks)
     "vit_test": SamConfig("vit_test", 64, 2, 2, (1,), img_size=256, patch_size=16, window_size=6,
                           out_chans=256),
+    # TinyViT-5M as MobileSAM / Light HQ-SAM ship it
+    "vit_t": TinyVitConfig("vit_t", (64, 128, 160, 320), (2, 2, 6, 2), (2, 4, 5, 10), (7, 7, 14, 7)),
+    # reduced TinyViT for tests: resolutions 64 / 32 / 16 / 16, grid 16 as vit_test; every layer pads its windows (32 -> 35,
+    # 16 -> 28, 16 -> 21); the last width stays 320 so that upstream's stride rule holds literally
+    "vit_t_test": TinyVitConfig("vit_t_test", (32, 64, 96, 320), (2, 1, 2, 1), (1, 2, 3, 10), (7, 7, 14, 7), img_size=256),
 }
 
 
-def init_sam_state_dict(cfg: SamConfig, seed: int = 72, hq: bool = False) -> "OrderedDict[str, torch.Tensor]":
-    """Random SAM weights with the upstream ``sam_vit_*.pth`` key layout; ``hq=True`` adds the HQ-SAM decoder extras of
-    ``sam_hq_vit_*.pth`` (m43/sam-hq @ 75c73fa, MaskDecoderHQ: SURVEY.md App. A-5)."""
-    w = _Init(seed)
+def _init_vit_encoder(w: _Init, cfg: SamConfig) -> None:
     D, g, hd = cfg.embed_dim, cfg.grid, cfg.head_dim
     C = cfg.out_chans
-    # ---- image encoder
     w.conv("image_encoder.patch_embed.proj", D, 3, cfg.patch_size, cfg.patch_size)
     w.normal("image_encoder.pos_embed", (1, g, g, D), 0.02)
     for i in range(cfg.depth):
@@ -352,6 +408,74 @@ def init_sam_state_dict(cfg: SamConfig, seed: int = 72, hq: bool = False) -> "Or
     w.norm("image_encoder.neck.1", C)
     w.conv("image_encoder.neck.2", C, C, 3, 3, bias=False)
     w.norm("image_encoder.neck.3", C)
+
+
+def _init_tinyvit_encoder(w: _Init, cfg: TinyVitConfig) -> None:
+    """TinyViT in upstream's key layout (tiny_vit_sam.py): ``Conv2d_BN`` = children ``c`` (bias-free Conv2d) and ``bn``.  The
+    BatchNorm statistics are off their defaults (running variance in [0.5, 1.5], non-zero means) and ``conv3.bn.weight`` is not
+    the zero upstream initialises it to, so that folding them is exercised; ``attention_biases`` get a spread that matters to the
+    softmax (std 0.5).  ``norm_head`` / ``head`` are in the checkpoints (TinyViT is built with its 1000-class head) and unused."""
+    e = "image_encoder."
+
+    def conv_bn(prefix, cin, cout, k, groups=1):
+        w.conv(prefix + ".c", cout, cin // groups, k, k, bias=False)
+        w.normal(prefix + ".bn.weight", (cout,), 0.1, mean=1.0)
+        w.normal(prefix + ".bn.bias", (cout,), 0.1)
+        w.normal(prefix + ".bn.running_mean", (cout,), 0.2)
+        w.uniform(prefix + ".bn.running_var", (cout,), 0.5)
+        w.sd[prefix + ".bn.running_var"] = w.sd[prefix + ".bn.running_var"] + 1.0          # in [0.5, 1.5]
+        w.sd[prefix + ".bn.num_batches_tracked"] = torch.tensor(1000, dtype=torch.long)
+
+    def merging(prefix, cin, cout, stride):
+        conv_bn(prefix + ".conv1", cin, cout, 1)
+        conv_bn(prefix + ".conv2", cout, cout, 3, groups=cout)
+        conv_bn(prefix + ".conv3", cout, cout, 1)
+
+    dims, C = cfg.embed_dims, cfg.out_chans
+    conv_bn(e + "patch_embed.seq.0", 3, dims[0] // 2, 3)
+    conv_bn(e + "patch_embed.seq.2", dims[0] // 2, dims[0], 3)
+    hid = dims[0] * cfg.mbconv_expand_ratio
+    for b in range(cfg.depths[0]):
+        p = f"{e}layers.0.blocks.{b}"
+        conv_bn(p + ".conv1", dims[0], hid, 1)
+        conv_bn(p + ".conv2", hid, hid, 3, groups=hid)
+        conv_bn(p + ".conv3", hid, dims[0], 1)
+    merging(e + "layers.0.downsample", dims[0], dims[1], cfg.merge_strides[0])
+    for i in range(1, 4):
+        D, ws = dims[i], cfg.window_sizes[i]
+        for b in range(cfg.depths[i]):
+            p = f"{e}layers.{i}.blocks.{b}"
+            w.normal(p + ".attn.attention_biases", (cfg.num_heads[i], ws * ws), 0.5)
+            w.norm(p + ".attn.norm", D)
+            w.linear(p + ".attn.qkv", 3 * D, D)
+            w.linear(p + ".attn.proj", D, D)
+            w.norm(p + ".mlp.norm", D)
+            w.linear(p + ".mlp.fc1", cfg.mlp_ratio * D, D)
+            w.linear(p + ".mlp.fc2", D, cfg.mlp_ratio * D)
+            conv_bn(p + ".local_conv", D, D, cfg.local_conv_size, groups=D)
+        if i < 3:
+            merging(f"{e}layers.{i}.downsample", D, dims[i + 1], cfg.merge_strides[i])
+    w.norm(e + "norm_head", dims[3])
+    w.linear(e + "head", 1000, dims[3])
+    w.conv(e + "neck.0", C, dims[3], 1, 1, bias=False)
+    w.norm(e + "neck.1", C)
+    w.conv(e + "neck.2", C, C, 3, 3, bias=False)
+    w.norm(e + "neck.3", C)
+
+
+def init_sam_state_dict(cfg, seed: int = 72, hq: bool = False) -> "OrderedDict[str, torch.Tensor]":
+    """Random SAM weights with the upstream ``sam_vit_*.pth`` key layout; ``hq=True`` adds the HQ-SAM decoder extras of
+    ``sam_hq_vit_*.pth`` (m43/sam-hq @ 75c73fa, MaskDecoderHQ: SURVEY.md App. A-5).  A ``TinyVitConfig`` gives the layout of
+    ``mobile_sam.pt`` / ``sam_hq_vit_tiny.pth``: the TinyViT encoder's keys (``_init_tinyvit_encoder``), the same prompt encoder
+    and decoder, the HQ extras at ``vit_dim = embed_dims[2]``.  That key map is restated from upstream's module tree and is
+    UNVERIFIED against a real checkpoint (none is available here)."""
+    w = _Init(seed)
+    C = cfg.out_chans
+    if isinstance(cfg, TinyVitConfig):
+        _init_tinyvit_encoder(w, cfg)
+    else:
+        _init_vit_encoder(w, cfg)
+    D = cfg.hq_dim
     # ---- prompt encoder
     w.normal("prompt_encoder.pe_layer.positional_encoding_gaussian_matrix", (2, C // 2), 1.0)
     for i in range(4):
