@@ -718,6 +718,25 @@ int sampt_seq_iou_counts(const uint64_t* dt_bits_dev, const int32_t* dt_area_dev
 int sampt_vis_match(const int64_t* counts_dev, int n_dt, int n_gt, int n_ranges, int n_thr, const double* thrs_dev,
                     const int32_t* gt_order_dev, const uint8_t* gt_ignore_dev, const uint8_t* iscrowd_dev, const uint8_t* dt_out_dev,
                     int32_t* dt_match_out_dev, int32_t* gt_match_out_dev, uint8_t* dt_ignore_out_dev, sampt_stream_t stream);
+/* Prediction overlays on the device (csrc/viz.hip; the definitions are those of sam_pt_amd/visualize.py, whose host restatement
+ * the results equal byte for byte).  No scratch memory, no atomics, integer work only: bitwise repeatable, stream-ordered.
+ * viz_band: bits_dev holds n bit-planes in the format of sampt_bits_pack (8-byte aligned); band_out_dev receives, in the same layout,
+ *   dil(m) & dil(~m): dil = binary dilation with the disk dy^2 + dx^2 <= radius^2 (0 <= radius <= 64), ~m the complement inside the
+ *   image only, everything outside the image 0 for both, the bits of rows >= h 0.  An empty mask, a full mask and radius 0 give zeros.
+ * viz_compose: frames_dev uint8 [n_frames][3][h][w], or [n_frames][h][w][3] with interleaved != 0; out_dev uint8 interleaved
+ *   [n_frames][h][w][3] for panel 1 (input: the frame and the markers) and panel 2 (predictions: the frame, then every mask's tint and
+ *   band, then the markers), [n_frames][2 h][w][3] for panel 3 (input above predictions, one pass).  bits_dev / band_dev: mask m of frame
+ *   t is plane m * n_frames + t (required when n_masks > 0 and the panel has predictions).  lut_dev uint8 [62][256], 4-byte aligned: a
+ *   pixel of mask m goes, channel by channel, through table (min(m, 9) * 3 + channel) * 2 + band if its mask bit is set and through table
+ *   60 + band if not, mask after mask; the host builds the tables.  markers_dev int32 [n_frames][n_markers][8] = centre x, centre y, kind
+ *   (0 = ring, 1 = cross), size (ring radius R / cross arm L), line width, reach (every covered pixel is within reach of the centre in
+ *   both axes), colour on the predictions panel, colour on the input panel (r | g << 8 | b << 16).  Markers are drawn in table order,
+ *   the last one that covers a pixel wins; centres may lie off the frame.  Pixels are read 4 per load from any byte address (widths
+ *   under 4: element by element, with the same result); out_dev 4-byte aligned and w % 4 == 0 gets 12-byte stores. */
+int sampt_viz_band(const uint64_t* bits_dev, int n, int h, int w, int radius, uint64_t* band_out_dev, sampt_stream_t stream);
+int sampt_viz_compose(const uint8_t* frames_dev, int interleaved, int n_frames, int h, int w, const uint64_t* bits_dev,
+                      const uint64_t* band_dev, int n_masks, const uint8_t* lut_dev, const int32_t* markers_dev, int n_markers, int panel,
+                      uint8_t* out_dev, sampt_stream_t stream);
 /* Whole SamPt.predict_mask chain (sam_pt.py:760-837) for `frames` independent (frame, object) items that share the
  * visible-point count k, batched into one launch sequence and without host synchronisation:
  * [positives-only pass over the first n_pos_first points when n_pos_first >= 0, i.e. negative_points_per_mask > 0;

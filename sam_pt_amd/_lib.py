@@ -170,6 +170,8 @@ _SIGS = {
     "sampt_seq_iou_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "sampt_seq_iou_counts": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "sampt_vis_match": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "sampt_viz_band": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
+    "sampt_viz_compose": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P, c_int, c_int, _P, _P]),
     "sampt_sam_track_decode": (c_int, [_P, c_int, _P, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_float, c_int, c_int, c_int,
                                        c_int, _P, _P, _P, c_size_t, _P]),
     "sampt_sam_track_decode_graph": (c_int, [_P, c_int, _P, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_float, c_int, c_int,

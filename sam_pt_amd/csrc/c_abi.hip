@@ -1202,6 +1202,26 @@ int sampt_vis_match(const int64_t* counts, int n_dt, int n_gt, int n_ranges, int
   return rc;
 }
 
+int sampt_viz_band(const uint64_t* bits, int n, int h, int w, int radius, uint64_t* band_out, sampt_stream_t stream) {
+  if (ve_bad_shape("sampt_viz_band", n, h, w) != SAMPT_OK) return SAMPT_ERR_ARG;
+  if (radius < 0 || radius > 64) return fail(SAMPT_ERR_ARG, "sampt_viz_band: radius must be in 0 .. 64");
+  int rc = viz_band((const unsigned long long*)bits, n, h, w, radius, (unsigned long long*)band_out, (hipStream_t)stream);
+  if (rc == SAMPT_ERR_ARG) return fail(rc, "sampt_viz_band: null or misaligned pointer");
+  return rc;
+}
+
+int sampt_viz_compose(const uint8_t* frames, int interleaved, int n_frames, int h, int w, const uint64_t* bits, const uint64_t* band,
+                      int n_masks, const uint8_t* lut, const int32_t* markers, int n_markers, int panel, uint8_t* out,
+                      sampt_stream_t stream) {
+  if (ve_bad_shape("sampt_viz_compose", n_frames, h, w) != SAMPT_OK) return SAMPT_ERR_ARG;
+  if (panel < 1 || panel > 3) return fail(SAMPT_ERR_ARG, "sampt_viz_compose: panel must be 1 (input), 2 (predictions) or 3 (stacked)");
+  if (n_masks < 0 || n_markers < 0) return fail(SAMPT_ERR_ARG, "sampt_viz_compose: negative n_masks or n_markers");
+  int rc = viz_compose(frames, interleaved, n_frames, h, w, (const unsigned long long*)bits, (const unsigned long long*)band, n_masks, lut,
+                       (const int*)markers, n_markers, panel, out, (hipStream_t)stream);
+  if (rc == SAMPT_ERR_ARG) return fail(rc, "sampt_viz_compose: null or misaligned pointer (masks need bits, band and lut; markers their table)");
+  return rc;
+}
+
 size_t sampt_jf_workspace_bytes(int n, int h, int w, int radius) { return jf_workspace_bytes(n, h, w, radius); }
 
 int sampt_jf_counts(const void* seg, int seg_kind, float seg_thr, const int32_t* seg_values, const int32_t* seg_planes, const void* ann,

@@ -424,6 +424,15 @@ int seq_iou_counts(const unsigned long long* dt_bits, const int* dt_area, const 
                    long long* counts, void* ws, size_t ws_bytes, hipStream_t s);
 int vis_match(const long long* counts, int D, int G, int A, int n_thr, const double* thrs, const int* gt_order, const unsigned char* gt_ignore,
               const unsigned char* iscrowd, const unsigned char* dt_out, int* dt_match, int* gt_match, unsigned char* dt_ignore, hipStream_t s);
+// ---- viz.hip: prediction overlays.  viz_band: bit-planes [n][nb][w] -> the contour band dil(m) & dil(~m) in the same layout (disk of
+// radius 0 .. 64, ~m inside the image only).  viz_compose: frames uint8 [T][3][h][w] (or interleaved [T][h][w][3]) -> out [T][h][w][3],
+// or [T][2 h][w][3] for panel 3; panel bit 0 = the input panel (frame + markers), bit 1 = the predictions panel (frame, per mask the
+// table of its colour / bit / band, then the markers).  bits / band: mask m of frame t is plane m * T + t; lut [62][256]; markers int32
+// [T][n_markers][8].
+int viz_band(const unsigned long long* bits, int n, int h, int w, int radius, unsigned long long* band, hipStream_t s);
+int viz_compose(const unsigned char* frames, int interleaved, int n_frames, int h, int w, const unsigned long long* bits,
+                const unsigned long long* band, int n_masks, const unsigned char* lut, const int* markers, int n_markers, int panel,
+                unsigned char* out, hipStream_t s);
 int bbox_from_logits_state(const float* logits, int h, int w, int* bbox_state, int* bbox_partial, hipStream_t s);
 // mask-input embedding (PromptEncoder.mask_downscaling, App. A-4) fused with "src = image_embedding + dense":
 //   mask (4g x 4g) -> conv2x2s2(1->c1) LN2d GELU -> conv2x2s2(c1->c2) LN2d GELU -> conv1x1(c2->256) ; src = feat + dense
