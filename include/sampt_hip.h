@@ -956,6 +956,40 @@ int sampt_vit_attention_f16(const void* qkv_dev, const float* rel_h_dev, const f
 int sampt_kmedoids_rowsums_f64(const float* xy_dev, int n, double* out_dev, sampt_stream_t stream);
 int sampt_kmedoids_alternate(const float* xy_dev, int n, int K, int32_t* medoids_dev, int max_iter, int32_t* iters_dev,
                              sampt_stream_t stream);
+/* Interactive point correction (sam_pt/modeling/sam_pt_interactive.py: the click simulator's DBSCAN and click rule) on the device.
+ *   dbscan_labels:  labels_out_dev int32 [n] equal to sklearn.cluster.DBSCAN(eps, min_samples).fit(X).labels_ element for element,
+ *                   by the order-free restatement in sam_pt_amd/interactive.py:dbscan_labels.  xy_dev: [n][2] f32 (row, col) pairs of
+ *                   INTEGER pixel coordinates in 0 .. 32767 (what mask.nonzero().float() yields), 1 <= n <= 2^20.  A pair is a
+ *                   neighbour iff its exact int32 squared distance is <= r2; the host passes r2 = floor(eps * eps) computed in
+ *                   float64, which equals scikit-learn's dist <= eps unless eps^2 is within rounding of an integer (the Python
+ *                   wrapper refuses such an eps).  The result does not depend on scheduling.  ws_dev: 16-byte aligned,
+ *                   sampt_dbscan_workspace_bytes(n) bytes (0 for an n out of range); stream-ordered, no host synchronisation, so
+ *                   what only the device can know comes back in the workspace: after the call its int32 word 0 is a status (0 = good;
+ *                   bit 0: a pointer chase of the union-find hit its hard cap of n + 8 steps, which a forest over n nodes cannot
+ *                   need - the kernels never spin; bit 1: a coordinate was no integer pixel in range) and word 1 the number of
+ *                   clusters.  A C caller must read word 0 after it has synchronised with the stream and treat a non-zero value as
+ *                   a failed call (the labels are then not valid): sampt_last_error cannot report what only the device knows
+ *                   without a synchronisation inside the call.  The Python wrapper does exactly that and raises.
+ *   dbscan_largest: Counter(labels).most_common(1) after -1 is removed: the largest cluster, on equal size the one whose first
+ *                   member has the smallest index.  members_out_dev int32 [n]: its member indices in ascending order (the order of
+ *                   mask_pixels[labels == id]).  info_out_dev int32 [4] = {id, size, number of clusters, id of the largest cluster};
+ *                   with no cluster, or a largest one below min_points, id is -1 ("use the whole mask") and no member is written.
+ *                   Same workspace size; it may be the one dbscan_labels used (words 0 .. 3 are left alone).
+ *   int_frame_state: one frame of the click rule (lines 330 - 361 of the reference).  logits_dev f32 [h][w] (mask = logits > 0),
+ *                   gt_dev bytes [h][w] (non-zero = object), points xy_dev f32 [n_points][2] (x, y), vis_dev f32 [n_points]
+ *                   (visible iff == 1), label_dev int32 [n_points] (1 = positive).  info_out_dev int32 [8] = {|TP|, |FN|, |FP|, first
+ *                   incorrect visible negative point or -1, first incorrect visible positive point or -1, 1 if a visible point's
+ *                   rounded coordinate is off the frame, 0, 0}; cat_out_dev bytes [n_points]: bit 0 visible, 1 positive, 2 correct,
+ *                   3 tp, 4 tn, 5 fp, 6 fn at the rounded coordinate (round half to even, as torch.round; -1 .. -size wraps as Python's
+ *                   indexing does, nothing is clamped); fn_out_dev / fp_out_dev: the FN and FP masks as byte planes [h][w]. */
+size_t sampt_dbscan_workspace_bytes(int n);
+int sampt_dbscan_labels(const float* xy_dev, int n, int r2, int min_samples, int32_t* labels_out_dev, void* ws_dev, size_t ws_bytes,
+                        sampt_stream_t stream);
+int sampt_dbscan_largest(const int32_t* labels_dev, int n, int min_points, int32_t* members_out_dev, int32_t* info_out_dev, void* ws_dev,
+                         size_t ws_bytes, sampt_stream_t stream);
+int sampt_int_frame_state(const float* logits_dev, const uint8_t* gt_dev, int h, int w, const float* xy_dev, const float* vis_dev,
+                          const int32_t* label_dev, int n_points, int32_t* info_out_dev, uint8_t* cat_out_dev, uint8_t* fn_out_dev,
+                          uint8_t* fp_out_dev, sampt_stream_t stream);
 /* Shi-Tomasi query points and mask erosion on the device (replaces the cv2 calls of
  * sam_pt/utils/query_points.py:102-162 extract_corner_points and :165-194 erode_mask_proportional_to_its_furthest_points_distance;
  * bit-identical to the numpy restatement of OpenCV's algorithms in sam_pt_amd/query_points.py).

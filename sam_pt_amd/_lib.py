@@ -252,6 +252,10 @@ _SIGS = {
     "sampt_vit_window_attention": (c_int, [c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P]),
     "sampt_kmedoids_rowsums_f64": (c_int, [_P, c_int, _P, _P]),
     "sampt_kmedoids_alternate": (c_int, [_P, c_int, c_int, _P, c_int, _P, _P]),
+    "sampt_dbscan_workspace_bytes": (c_size_t, [c_int]),
+    "sampt_dbscan_labels": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "sampt_dbscan_largest": (c_int, [_P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "sampt_int_frame_state": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P, _P, _P]),
     "sampt_qp_corners_workspace_bytes": (c_int, [c_int, c_int, C.POINTER(c_size_t)]),
     "sampt_qp_erode_u8": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
     "sampt_qp_shi_tomasi": (c_int, [_P, _P, c_int, c_int, c_int, c_float, _P, _P, _P, c_size_t, _P]),

@@ -1392,6 +1392,30 @@ int sampt_kmedoids_alternate(const float* xy, int n, int K, int32_t* medoids, in
   return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_kmedoids_alternate: bad arguments (1 <= K <= min(n, 64), n <= 2048)") : rc;
 }
 
+size_t sampt_dbscan_workspace_bytes(int n) { return dbscan_workspace_bytes(n); }
+
+int sampt_dbscan_labels(const float* xy, int n, int r2, int min_samples, int32_t* labels_out, void* ws, size_t ws_bytes,
+                        sampt_stream_t stream) {
+  int rc = dbscan_labels(xy, n, r2, min_samples, (int*)labels_out, ws, ws_bytes, (hipStream_t)stream);
+  if (rc == SAMPT_ERR_WORKSPACE) return fail(rc, "sampt_dbscan_labels: workspace smaller than sampt_dbscan_workspace_bytes(n)");
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_dbscan_labels: bad arguments (1 <= n <= 2^20, r2 >= 0, min_samples >= 1, 16-byte aligned workspace)") : rc;
+}
+
+int sampt_dbscan_largest(const int32_t* labels, int n, int min_points, int32_t* members_out, int32_t* info_out, void* ws, size_t ws_bytes,
+                         sampt_stream_t stream) {
+  int rc = dbscan_largest((const int*)labels, n, min_points, (int*)members_out, (int*)info_out, ws, ws_bytes, (hipStream_t)stream);
+  if (rc == SAMPT_ERR_WORKSPACE) return fail(rc, "sampt_dbscan_largest: workspace smaller than sampt_dbscan_workspace_bytes(n)");
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_dbscan_largest: bad arguments (1 <= n <= 2^20, 16-byte aligned workspace)") : rc;
+}
+
+int sampt_int_frame_state(const float* logits, const uint8_t* gt, int h, int w, const float* xy, const float* vis, const int32_t* label,
+                          int n_points, int32_t* info_out, uint8_t* cat_out, uint8_t* fn_out, uint8_t* fp_out, sampt_stream_t stream) {
+  if ((long)h * w >= (1L << 31)) return fail(SAMPT_ERR_ARG, "sampt_int_frame_state: h * w must be below 2^31");
+  int rc = int_frame_state(logits, gt, h, w, xy, vis, (const int*)label, n_points, (int*)info_out, cat_out, fn_out, fp_out,
+                           (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_int_frame_state: null pointer or bad shape") : rc;
+}
+
 int sampt_qp_corners_workspace_bytes(int H, int W, size_t* bytes) {
   if (!bytes || H < 3 || W < 3) return fail(SAMPT_ERR_ARG, "sampt_qp_corners_workspace_bytes: bad arguments");
   *bytes = qp_corners_workspace_bytes(H, W);

@@ -91,6 +91,18 @@ int kmedoids_rowsums(const float* xy, int n, double* out, hipStream_t s);
 // medoids: device int [K], in = the initial medoids, out = the converged ones; iters_out (device int, optional) = iterations run
 int kmedoids_alternate(const float* xy, int n, int K, int* medoids, int max_iter, int* iters_out, hipStream_t s);
 
+// ---- dbscan.hip (interactive point correction, sam_pt/modeling/sam_pt_interactive.py:330-395, 678-729; labels equal to
+// sklearn.cluster.DBSCAN's element for element, restated in sam_pt_amd/interactive.py)
+// xy: device [n][2] f32 integer pixel coordinates (row, col) in 0 .. 32767, n <= 2^20; neighbours: d^2 <= r2.  labels int32 [n].
+// ws (16-byte aligned, dbscan_workspace_bytes(n)): word 0 = status after the call (0 = good), word 1 = number of clusters
+size_t dbscan_workspace_bytes(int n);
+int dbscan_labels(const float* xy, int n, int r2, int min_samples, int* labels, void* ws, size_t ws_bytes, hipStream_t s);
+// members int32 [n] (ascending indices of the chosen cluster), info int32 [4] = chosen id or -1, its size, clusters, largest id
+int dbscan_largest(const int* labels, int n, int min_points, int* members, int* info, void* ws, size_t ws_bytes, hipStream_t s);
+// frame state of the click rule: info int32 [8], cat u8 [n_points], fn / fp byte planes [h][w]
+int int_frame_state(const float* logits, const unsigned char* gt, int h, int w, const float* xy, const float* vis, const int* label,
+                    int n_points, int* info, unsigned char* cat, unsigned char* fn_out, unsigned char* fp_out, hipStream_t s);
+
 // ---- corners.hip (Shi-Tomasi query points + mask erosion, sam_pt/utils/query_points.py:102-194; bit-identical to the numpy
 // restatement in sam_pt_amd/query_points.py)
 size_t qp_corners_workspace_bytes(int H, int W);
