@@ -737,6 +737,23 @@ int sampt_viz_band(const uint64_t* bits_dev, int n, int h, int w, int radius, ui
 int sampt_viz_compose(const uint8_t* frames_dev, int interleaved, int n_frames, int h, int w, const uint64_t* bits_dev,
                       const uint64_t* band_dev, int n_masks, const uint8_t* lut_dev, const int32_t* markers_dev, int n_markers, int panel,
                       uint8_t* out_dev, sampt_stream_t stream);
+/* Patch-similarity filter of SamPt._track_points (csrc/patch_filter.hip; the definitions are those of sam_pt_amd/sam_pt.py:
+ * rgb2lab and SamPt._patch_similarity_filter, reference sam_pt.py:597-690).  One launch, no scratch memory, stream-ordered, bitwise
+ * repeatable.  rgb_dev uint8 [T][3][H][W]; query_dev f32 [N][3] = (t, x, y); traj_dev f32 [T][N][2]; vis_in_dev f32 [T][N];
+ * companding_dev float64 [256]: the sRGB companding of byte / 255 as the host's rgb2lab computes it (sam_pt_amd/patch_filter.py
+ * builds it); vis_out_dev f32 [T][N], a buffer of its own; sim_out_dev f32 [T][N] or null.
+ * Per item: the CIELAB patch (taps -(ps/2) .. ps/2 on both axes, i.e. ps + 1 per side for an even ps; bilinear, corners outside the
+ * frame 0) around the trajectory point against the patch around the query point on the query frame,
+ * sim = exp(-||difference||_2 / (2 ps^2)); vis == 1 and not sim > threshold -> -3.  Per point: everything after the first -3 after
+ * the query frame and everything before the first -3 before it -> -4.  border_rule != 0: then x / W < 0.01, y / H < 0.01,
+ * x / W > 0.99 or y / H > 0.99 (f32, IEEE division) -> -2.  With sim_out_dev the similarity of EVERY item is written; without it the
+ * items with vis != 1 are not sampled.  An item with a non-finite coordinate, and every item of a point whose query is non-finite or
+ * names a frame outside 0 .. T - 1, is non-similar (similarity 0).
+ * SAMPT_ERR_ARG: a null pointer other than sim_out_dev; T, N, H or W <= 0; patch_size outside 1 .. 15. */
+#define SAMPT_PATCH_FILTER_MAX_PATCH_SIZE 15
+int sampt_patch_filter(const uint8_t* rgb_dev, int T, int H, int W, const float* query_dev, const float* traj_dev,
+                       const float* vis_in_dev, int N, int patch_size, float threshold, const double* companding_dev, int border_rule,
+                       float* vis_out_dev, float* sim_out_dev, sampt_stream_t stream);
 /* Whole SamPt.predict_mask chain (sam_pt.py:760-837) for `frames` independent (frame, object) items that share the
  * visible-point count k, batched into one launch sequence and without host synchronisation:
  * [positives-only pass over the first n_pos_first points when n_pos_first >= 0, i.e. negative_points_per_mask > 0;

@@ -172,6 +172,7 @@ _SIGS = {
     "sampt_vis_match": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "sampt_viz_band": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "sampt_viz_compose": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P, c_int, c_int, _P, _P]),
+    "sampt_patch_filter": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_float, _P, c_int, _P, _P, _P]),
     "sampt_sam_track_decode": (c_int, [_P, c_int, _P, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_float, c_int, c_int, c_int,
                                        c_int, _P, _P, _P, c_size_t, _P]),
     "sampt_sam_track_decode_graph": (c_int, [_P, c_int, _P, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_float, c_int, c_int,

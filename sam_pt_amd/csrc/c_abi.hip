@@ -1210,6 +1210,22 @@ int sampt_viz_band(const uint64_t* bits, int n, int h, int w, int radius, uint64
   return rc;
 }
 
+static_assert(SAMPT_PATCH_FILTER_MAX_PATCH_SIZE == PATCH_FILTER_MAX_PATCH_SIZE, "header and kernel disagree");
+int sampt_patch_filter(const uint8_t* rgb, int T, int H, int W, const float* query, const float* traj, const float* vis_in, int N,
+                       int patch_size, float threshold, const double* companding, int border_rule, float* vis_out, float* sim_out,
+                       sampt_stream_t stream) {
+  if (T <= 0 || N <= 0 || H <= 0 || W <= 0)
+    return fail(SAMPT_ERR_ARG, "sampt_patch_filter: T, N, H and W must be positive; got T = " + std::to_string(T) + ", N = " +
+                                   std::to_string(N) + ", H = " + std::to_string(H) + ", W = " + std::to_string(W));
+  if (patch_size < 1 || patch_size > SAMPT_PATCH_FILTER_MAX_PATCH_SIZE)
+    return fail(SAMPT_ERR_ARG, "sampt_patch_filter: patch_size must be in 1 .. " + std::to_string(SAMPT_PATCH_FILTER_MAX_PATCH_SIZE) +
+                                   "; got " + std::to_string(patch_size));
+  if (!rgb || !query || !traj || !vis_in || !companding || !vis_out)
+    return fail(SAMPT_ERR_ARG, "sampt_patch_filter: null pointer (only sim_out may be null)");
+  return patch_filter(rgb, T, H, W, query, traj, vis_in, N, patch_size, threshold, companding, border_rule, vis_out, sim_out,
+                      (hipStream_t)stream);
+}
+
 int sampt_viz_compose(const uint8_t* frames, int interleaved, int n_frames, int h, int w, const uint64_t* bits, const uint64_t* band,
                       int n_masks, const uint8_t* lut, const int32_t* markers, int n_markers, int panel, uint8_t* out,
                       sampt_stream_t stream) {

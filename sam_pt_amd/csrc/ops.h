@@ -445,6 +445,13 @@ int viz_band(const unsigned long long* bits, int n, int h, int w, int radius, un
 int viz_compose(const unsigned char* frames, int interleaved, int n_frames, int h, int w, const unsigned long long* bits,
                 const unsigned long long* band, int n_masks, const unsigned char* lut, const int* markers, int n_markers, int panel,
                 unsigned char* out, hipStream_t s);
+// ---- patch_filter.hip: the patch-similarity filter of SamPt._track_points (sam_pt.py:597-690) in one launch, one workgroup per point.
+// rgb uint8 [T][3][H][W], query f32 [N][3] = (t, x, y), traj f32 [T][N][2], vis_in f32 [T][N], companding = the 256-entry float64
+// sRGB table of the host; vis_out f32 [T][N] (not vis_in), sim_out f32 [T][N] or null.  patch_size 1 .. PATCH_FILTER_MAX_PATCH_SIZE.
+#define PATCH_FILTER_MAX_PATCH_SIZE 15
+int patch_filter(const unsigned char* rgb, int T, int H, int W, const float* query, const float* traj, const float* vis_in, int N,
+                 int patch_size, float threshold, const double* companding, int border_rule, float* vis_out, float* sim_out,
+                 hipStream_t s);
 int bbox_from_logits_state(const float* logits, int h, int w, int* bbox_state, int* bbox_partial, hipStream_t s);
 // mask-input embedding (PromptEncoder.mask_downscaling, App. A-4) fused with "src = image_embedding + dense":
 //   mask (4g x 4g) -> conv2x2s2(1->c1) LN2d GELU -> conv2x2s2(c1->c2) LN2d GELU -> conv1x1(c2->256) ; src = feat + dense

@@ -19,8 +19,10 @@ Also built: ``query_masks`` mode with host-side query
 (``sam_pt_amd/query_points.py``: random and k-medoids) and point re-initialisation with all four ``reinit_variant``s
 (sam_pt.py:355-543), re-using the cached image embeddings across re-initialisation segments.
 Shi-Tomasi / "mixed" point selection restate OpenCV's algorithms on the host (parity unpinned, query_points.py).
-The optional patch-similarity filter (sam_pt.py:597-682, off in every shipped config) is built on the host with a
-restated ``rgb2lab`` (skimage absent: that one function is parity unpinned).
+The optional patch-similarity filter (sam_pt.py:597-682, off in every shipped config) is built twice: on the host with a
+restated ``rgb2lab`` (skimage absent: that one function is parity unpinned), which is what runs on CPU tensors, and as one
+HIP launch (``sam_pt_amd/patch_filter.py``, held to the host restatement), which is what runs when the tracker's results are
+HIP tensors.
 """
 from __future__ import annotations
 
@@ -86,6 +88,9 @@ class PendingForward:
 
 
 class SamPt(nn.Module):
+    # the patch-similarity filter of a tracker whose results are HIP tensors runs in csrc/patch_filter.hip; False forces the host path
+    patch_filter_on_device = True
+
     def __init__(self, point_tracker, sam_predictor, sam_iou_threshold: float,
                  positive_point_selection_method: str = "kmedoids", negative_point_selection_method: str = "mixed",
                  positive_points_per_mask: int = 8, negative_points_per_mask: int = 0,
@@ -557,16 +562,34 @@ class SamPt(nn.Module):
                 out = self.point_tracker.to(self.device).evaluate_batch(rgbs_dev, q.reshape(1, m * p, 3).to(self.device))
             t = out["trajectories_pred"].squeeze(0)
             v = out["visibilities_pred"].squeeze(0).float()
-            if self.use_patch_matching_filtering:
-                v = self._patch_similarity_filter(rgbs, q.reshape(m * p, 3).cpu(), t, v, m, p)
-            h, w = rgbs.shape[-2:]
-            v[t[:, :, 0] / w < 0.01] = PointVisibilityType.OUTSIDE_FRAME.value   # sam_pt.py:684-690
-            v[t[:, :, 1] / h < 0.01] = PointVisibilityType.OUTSIDE_FRAME.value
-            v[t[:, :, 0] / w > 0.99] = PointVisibilityType.OUTSIDE_FRAME.value
-            v[t[:, :, 1] / h > 0.99] = PointVisibilityType.OUTSIDE_FRAME.value
+            hw = rgbs.shape[-2:]
+            if self.use_patch_matching_filtering and t.is_cuda and self.patch_filter_on_device:
+                # a tracker that leaves its results on the HIP device: filter and border rule in one launch, on the frames as they
+                # stand in rgbs_dev (sam_pt_amd/patch_filter.py)
+                from .patch_filter import patch_similarity_filter
+                v = patch_similarity_filter(rgbs_dev[0], q.reshape(m * p, 3).to(t.device), t, v, self.patch_size,
+                                            self.patch_similarity_threshold, border_rule=True)
+            elif self.use_patch_matching_filtering and t.is_cuda:
+                # ... forced to the host: everything on CPU copies, the border comparisons too (where the reference evaluates them)
+                t_host = t.cpu()
+                v_host = self._patch_similarity_filter(rgbs, q.reshape(m * p, 3).cpu(), t_host, v.cpu(), m, p)
+                self._mark_outside_frame(t_host, v_host, *hw)
+                v = v_host.to(t.device)
+            else:
+                if self.use_patch_matching_filtering:
+                    v = self._patch_similarity_filter(rgbs, q.reshape(m * p, 3).cpu(), t, v, m, p)
+                self._mark_outside_frame(t, v, *hw)
             trajs.append(t.reshape(-1, m, p, 2))
             viss.append(v.reshape(-1, m, p))
         return torch.cat(trajs, dim=1), torch.cat(viss, dim=1)
+
+    @staticmethod
+    def _mark_outside_frame(t, v, h, w):
+        """The four border comparisons of sam_pt.py:684-690 on t (T,N,2) and v (T,N), in place."""
+        v[t[:, :, 0] / w < 0.01] = PointVisibilityType.OUTSIDE_FRAME.value
+        v[t[:, :, 1] / h < 0.01] = PointVisibilityType.OUTSIDE_FRAME.value
+        v[t[:, :, 0] / w > 0.99] = PointVisibilityType.OUTSIDE_FRAME.value
+        v[t[:, :, 1] / h > 0.99] = PointVisibilityType.OUTSIDE_FRAME.value
 
     # ------------------------------------------------------------------------------------------------
     def _patch_similarity_filter(self, rgbs, query_points, traj, vis, n_masks, n_pts):
