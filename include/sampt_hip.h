@@ -783,6 +783,14 @@ int sampt_sam_track_decode_graph(sampt_dec_t h, int frames, const float* feature
                                  int in_h, int in_w, int out_h, int out_w, float* final_logits_dev, float* score_out_dev,
                                  void* workspace_dev, size_t workspace_bytes, sampt_stream_t stream);
 int sampt_dec_graph_stats(sampt_dec_t h, long* cached, long* captures, long* launches);
+/* Batch-invariant decoding (on = 1; a new handle has it off).  Off, the decoder's latency-bound f32 products choose their kernel by
+ * total row count and the token -> image attention splits its keys by the number of workgroups, so an item's logits depend — in the
+ * last bits — on how many items share its call.  On, every item of sampt_sam_decode / _decode_multimask / _decode_points /
+ * _track_decode / _track_decode_graph gets the bits it gets alone: the plain f32 products take the row-invariant route
+ * (sampt_gemm_f32_route, invariant = 1), the attention's key split is that of sampt_attn_t2i_plan(invariant = 1), and the image
+ * side is told from the token side by the rows of one item.  The workspace sizes the handle reports hold in either mode; captured
+ * graphs are keyed by the mode.  The results of the two modes differ from each other by rounding (a few 1e-7 relative). */
+int sampt_dec_set_batch_invariant(sampt_dec_t h, int on);
 int sampt_postprocess_masks(const float* low_res_dev, int L, int img_size, int in_h, int in_w, float* out_dev, int out_h,
                             int out_w, sampt_stream_t stream);
 /* bbox_state_dev: int32[5] = {xmin, ymin, xmax, ymax, count} over logits > 0 (sam_pt.py:809-820). */
@@ -825,6 +833,17 @@ int sampt_gemm(int dtype, const void* A_dev, const void* W_dev, const float* bia
 /* The same GEMM with the row maps the ViT engine uses: rowmap[m] = destination row of C / res for GEMM row m (-1 drops the
  * row; C must hold max(rowmap)+1 rows), a_rowmap[m] = row of A read by GEMM row m (gather), res_mod > 0: the residual row
  * is (destination row) % res_mod (broadcast over the batch, e.g. a positional embedding), ldr = row stride of res (0: N). */
+/* The plain f32 product as the mask decoder issues it: C[m][n] = act(A[m * lda ..] . W[n][K] + bias[n]) (+ res[(m % res_mod)][n],
+ * res_mod = 0: res[m][n]); lda / ldc = 0: K / N; workspace_dev: optional split-K workspace of the default routes.
+ * invariant = 1: the row-invariant route — row m's bits are a function of its K inputs, K, N, the leading dimensions and the
+ * pointers' alignment alone, whatever M is and wherever the row sits.
+ * sampt_gemm_f32_route (host only): the kernel that call takes for 16-byte aligned operands and the decoder's split-K workspace —
+ * route 0 skinny, 1 thin, 2 tiled, 3 row-invariant thin, 4 row-invariant one-wave-per-element — and the number of K partitions whose
+ * partial sums are added at the end (lanes, waves or split-K slices). */
+int sampt_gemm_f32_rows(const float* A_dev, int lda, const float* W_dev, const float* bias_dev, const float* res_dev, int res_mod,
+                        float* C_dev, int ldc, int M, int N, int K, int act, int invariant, void* workspace_dev,
+                        size_t workspace_bytes, sampt_stream_t stream);
+int sampt_gemm_f32_route(int M, int N, int K, int lda, int ldc, int invariant, int* route, int* kparts);
 int sampt_gemm_ex(int dtype, const void* A_dev, const void* W_dev, const float* bias_dev, const float* res_dev,
                   void* C_dev, int M, int N, int K, int act, float alpha, const int32_t* rowmap_dev,
                   const int32_t* a_rowmap_dev, int res_mod, int ldr, sampt_stream_t stream);
@@ -951,6 +970,10 @@ int sampt_attention_f32(int kind, const float* q_dev, const float* k_dev, const 
 int sampt_attention_t2i_workspace_bytes(int F, int Nq, int Nk, size_t* bytes);
 int sampt_attention_t2i_f32(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, int F, int Nq, int Nk,
                             void* workspace_dev, size_t workspace_bytes, sampt_stream_t stream);
+/* The key split of that attention (host only): KS workgroups of kper keys per (item, 8 queries), one partial softmax state of
+ * 144 floats per (item, query, split).  invariant = 0: chosen to fill the chip, so it shrinks as F * ceil(Nq / 8) grows;
+ * invariant = 1 (sampt_dec_set_batch_invariant): a function of Nk alone.  sampt_attention_t2i_workspace_bytes covers both. */
+int sampt_attn_t2i_plan(int F, int Nq, int Nk, int invariant, int* KS, int* kper);
 /* CoTracker's UpdateFormer attention straight from packed qkv rows [rows][3*heads*hd] (timm Attention): token t of group b
  * is row b*batch_stride_rows + t*token_stride_rows (time attention: S, 1; space attention: 1, S); out [rows][heads*hd]. */
 int sampt_cotracker_attention_f32(const float* qkv_dev, float* out_dev, int nbatch, int L, int batch_stride_rows,

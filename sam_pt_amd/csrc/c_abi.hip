@@ -70,6 +70,7 @@ struct DecGraphKey {
   const void *features, *hq, *pts, *labels, *k_item, *npos_item, *logits, *score, *ws;
   size_t ws_bytes;
   int frames, k, ld_pts, n_pos_first, refine, in_h, in_w, oh, ow;
+  int batch_invariant;   // DecEngine::batch_invariant at capture: a graph holds the kernels of ONE mode
   float iou_thr;
   bool operator==(const DecGraphKey& o) const { return memcmp(this, &o, sizeof(*this)) == 0; }
 };
@@ -965,6 +966,12 @@ int sampt_dec_create(const char* const* names, const void* const* ptrs, int n, i
 }
 void sampt_dec_destroy(sampt_dec_t h) { delete h; }
 
+int sampt_dec_set_batch_invariant(sampt_dec_t h, int on) {
+  if (!h || on < 0 || on > 1) return fail(SAMPT_ERR_ARG, "sampt_dec_set_batch_invariant: null handle, or a value other than 0 / 1");
+  h->e.batch_invariant = on != 0;     // (captured graphs are keyed by the mode: none is replayed across a change)
+  return SAMPT_OK;
+}
+
 int sampt_dec_workspace_bytes_k(sampt_dec_t h, int frames, int k, int oh, int ow, size_t* bytes) {
   if (!h || !bytes) return fail(SAMPT_ERR_ARG, "sampt_dec_workspace_bytes_k: null handle / output");
   if (frames <= 0 || frames > h->e.max_frames)
@@ -1313,6 +1320,7 @@ int sampt_sam_track_decode_graph(sampt_dec_t h, int frames, const float* feature
   key.npos_item = npos_item, key.logits = final_logits, key.score = score_out, key.ws = ws, key.ws_bytes = ws_bytes;
   key.frames = frames, key.k = k, key.ld_pts = ld_pts, key.n_pos_first = n_pos_first, key.refine = refine_iters;
   key.in_h = in_h, key.in_w = in_w, key.oh = oh, key.ow = ow, key.iou_thr = iou_thr;
+  key.batch_invariant = h->e.batch_invariant ? 1 : 0;
   try {
     DecGraphEntry& ent = h->graphs[key];
     ent.last_use = ++h->graph_clock;
@@ -1383,6 +1391,35 @@ int sampt_gemm(int dtype, const void* A, const void* W, const float* bias, const
   GemmP p = gemm_linear(A, K, W, bias, C, N, M, N, K, act, res);
   p.alpha = alpha, p.out_f16 = dtype == 2;
   return dtype == 0 ? gemm_f32(p, (hipStream_t)stream) : gemm_f16(p, (hipStream_t)stream);
+}
+
+int sampt_gemm_f32_rows(const float* A, int lda, const float* W, const float* bias, const float* res, int res_mod, float* C, int ldc,
+                        int M, int N, int K, int act, int invariant, void* ws, size_t ws_bytes, sampt_stream_t stream) {
+  if (invariant < 0 || invariant > 1) return fail(SAMPT_ERR_ARG, "sampt_gemm_f32_rows: invariant is 0 or 1");
+  GemmP p = gemm_linear(A, lda > 0 ? lda : K, W, bias, C, ldc > 0 ? ldc : N, M, N, K, act, res, N, res_mod);
+  p.row_invariant = invariant;
+  p.splitk_ws = (float*)ws, p.splitk_ws_floats = ws ? ws_bytes / sizeof(float) : 0;
+  int rc = gemm_f32(p, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_gemm_f32_rows: null / misaligned operand, or K, lda not a multiple of 4") : rc;
+}
+
+int sampt_gemm_f32_route(int M, int N, int K, int lda, int ldc, int invariant, int* route, int* kparts) {
+  if (M <= 0 || N <= 0 || K <= 0 || lda < 0 || ldc < 0 || invariant < 0 || invariant > 1 || !route || !kparts)
+    return fail(SAMPT_ERR_ARG, "sampt_gemm_f32_route: bad arguments");
+  // the decoder's call: 16-byte aligned operands, bias, no residual, its split-K workspace of 16 * M * 256 floats (never dereferenced)
+  float* const aligned = (float*)(uintptr_t)4096;
+  GemmP p = gemm_linear(aligned, lda > 0 ? lda : K, aligned, aligned, aligned, ldc > 0 ? ldc : N, M, N, K, ACT_NONE, nullptr, N, 0);
+  p.row_invariant = invariant;
+  p.splitk_ws = aligned, p.splitk_ws_floats = (size_t)16 * M * 256;
+  int rc = gemm_f32_route(p, route, kparts);
+  return rc == SAMPT_OK ? rc : fail(rc, "sampt_gemm_f32_route: K must be a multiple of 4");
+}
+
+int sampt_attn_t2i_plan(int F, int Nq, int Nk, int invariant, int* KS, int* kper) {
+  if (F <= 0 || Nq <= 0 || Nk <= 0 || invariant < 0 || invariant > 1 || !KS || !kper)
+    return fail(SAMPT_ERR_ARG, "sampt_attn_t2i_plan: bad arguments");
+  attn_t2i_plan_query(F, Nq, Nk, invariant != 0, KS, kper);
+  return SAMPT_OK;
 }
 
 int sampt_gemm_ex(int dtype, const void* A, const void* W, const float* bias, const float* res, void* C, int M, int N, int K,

@@ -197,6 +197,10 @@ struct GemmP {
   int p8_wgs = 0;                // gemm_f16_p8: persistent workgroups per XCD (0: one per CU = 32); fewer leaves whole CUs free
   int p8_stagger = 0;            // gemm_f16_p8: phase groups of the persistent workgroups (0: the process-wide setting; 1: off)
   int force_generic = 0;         // tests: bypass the specialised LDS-DMA fp16 kernel
+  // plain f32 products only (gemm.hip, plan_route_f32): the kernel is chosen from K, N, the leading dimensions and the pointers'
+  // alignment and sums every row of C in an order that K alone fixes — a row's result does not depend on M, on the row's place
+  // in the matrix or on the split-K workspace (the mask decoder's batch-invariant mode, DecEngine::batch_invariant)
+  int row_invariant = 0;
   int splitk = 1;
   float* splitk_ws = nullptr;
   size_t splitk_ws_floats = 0;
@@ -228,6 +232,10 @@ int gemm_f32(const GemmP& p, hipStream_t s);
 int gemm_f16(const GemmP& p, hipStream_t s);
 // the split-K factor gemm_f32 will choose for this problem (1 = no split; needs p.splitk_ws / splitk_ws_floats set)
 int gemm_f32_plan_splitk(const GemmP& p);
+// the kernel gemm_f32 will launch for this problem and the number of K partitions whose partial sums it adds at the end (lanes of a
+// wave, waves of a workgroup, split-K slices); host only, nothing is launched
+enum { GEMM_ROUTE_SKINNY = 0, GEMM_ROUTE_THIN = 1, GEMM_ROUTE_TILED = 2, GEMM_ROUTE_INV_THIN = 3, GEMM_ROUTE_INV_ROWDOT = 4 };
+int gemm_f32_route(const GemmP& p, int* route, int* kparts);
 // fp32-grade convolution on the fp16 pipe: f32 NHWC activations, weights pre-split into fp16 hi/lo planes scaled by
 // 2^F16X3_WSHIFT (conv_f16x3.hip); the caller sets alpha = 2^-F16X3_WSHIFT.  Cin % 32 == 0.
 #define F16X3_WSHIFT 8

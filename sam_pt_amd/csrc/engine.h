@@ -384,6 +384,10 @@ struct DecEngine {
   const int *up0_map, *up1_map;                  // pixel-shuffle row maps [4][max_frames*g*g], [4][max_frames*4*g*g]
   const float *hyp_w[3], *hyp_b[3], *iou_w[3], *iou_b[3];         // hypernetwork MLP 0 and IoU head
   const float *hypx_w[3][3], *hypx_b[3][3];                       // hypernetwork MLPs 1..3 (multimask_output=True)
+  // Batch-invariant decoding (sampt_dec_set_batch_invariant): an item's result does not depend on what shares its launch sequence.
+  // Every plain f32 product takes GemmP::row_invariant, attn_t2i splits its keys by Nk alone, and the image / token side of
+  // L::lin is told apart by the rows of one item.  Off: the routes by total row count, bit for bit as before.
+  bool batch_invariant = false;
   bool multimask = false;  // next decode(): SAM's multimask_output=True — 3 masks / IoUs of mask tokens 1..3 (F == 1, SAM only)
   // HQ-SAM extras (c.vit_dim > 0): out_tokens has a 6th row (hf_token); ConvT weights packed like up0/up1
   struct HqW {

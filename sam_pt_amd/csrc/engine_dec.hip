@@ -113,11 +113,15 @@ struct L {
   float* skws;
   size_t skn;
   const std::unordered_map<const float*, const half_t*>* w_hl = nullptr;
+  int F = 1;             // items of the launch sequence (frames / prompts)
+  bool inv = false;      // DecEngine::batch_invariant: no decision below may look at F
   int lin(const float* A, int M, int K, const float* W, const float* b, float* C, int N, int act = ACT_NONE,
           const float* res = nullptr, int lda = 0, int res_mod = 0, int ldc = 0) const {
     GemmP p = gemm_linear(A, lda ? lda : K, W, b, C, ldc ? ldc : N, M, N, K, act, res, N, res_mod);   // res_mod: the residual is a block of res_mod rows, broadcast
     p.splitk_ws = skws, p.splitk_ws_floats = skn;
-    if (w_hl && M >= 2048 && !lda && !ldc && K % 32 == 0 && N % 4 == 0) {     // image-token projections, split-fp16 planes packed
+    p.row_invariant = inv;
+    const int rows = inv && M >= F ? M / F : M;      // batch-invariant: the image / token side is told apart by the rows of ONE item
+    if (w_hl && rows >= 2048 && !lda && !ldc && K % 32 == 0 && N % 4 == 0) {     // image-token projections, split-fp16 planes packed
       auto it = w_hl->find(W);
       if (it != w_hl->end()) {
         gemm_split_planes(p, it->second);
@@ -140,6 +144,7 @@ struct Bufs {
 // fused image-side projection: out [M][f.n] = A W^T + b + pe[row % P]   (see DecEngine::FusedProj)
 static int fused_proj(const L& l, const DecEngine::FusedProj& f, const float* A, long M, int C, int P, float* out) {
   GemmP p = gemm_linear(A, C, f.w, f.b, out, f.n, (int)M, f.n, C, ACT_NONE, f.pe, f.n, P);
+  p.row_invariant = l.inv;
   if (f.hl && C % 32 == 0) {
     gemm_split_planes(p, f.hl);
     return conv_f16x3(p, l.s);
@@ -150,7 +155,10 @@ static int fused_proj(const L& l, const DecEngine::FusedProj& f, const float* A,
 // tail of an attention block: out = LN(resid + out_proj(att))
 static int attn_tail(const L& l, const DecEngine::Attn& a, int C, long rows, const float* att, const float* resid, float* out,
                      const float* lnw, const float* lnb, hipStream_t s) {
-  if (l.w_hl && resid && g_gemm_x3_wres && g_gemm_x3_epi) {      // image-token side at scale: projection + residual + LayerNorm in one kernel
+  // (batch-invariant: only where L::lin below would take the split-fp16 planes for ONE item's rows too — the fused kernel is that
+  //  product bit for bit, the f32 product it would otherwise displace at F * rows >= 16384 is not)
+  const bool x3_rows = !l.inv || rows / l.F >= 2048;
+  if (l.w_hl && resid && g_gemm_x3_wres && g_gemm_x3_epi && x3_rows) {      // image-token side at scale: projection + residual + LayerNorm in one kernel
     auto it = l.w_hl->find(a.ow);
     if (it != l.w_hl->end()) {
       GemmP p = gemm_linear(att, a.inner, a.ow, a.ob, out, C, (int)rows, C, a.inner, ACT_NONE, resid, C);
@@ -173,7 +181,7 @@ static int attn_block(const L& l, const DecEngine::Attn& a, int heads, int C, in
   const int hd = a.inner / heads;
   if (few_keys) SAMPT_TRY(attn_fewkeys(b.Q, b.K, b.V, b.att, F, Nq, Nk, heads, hd, nk_item, s));
   else if (hd == 16 && heads == 8 && Nk > 256 && !nk_item)     // token -> image: the K / V stream decides, read it once
-    SAMPT_TRY(attn_t2i(b.Q, b.K, b.V, b.att, F, Nq, Nk, b.part, b.part_floats, s));
+    SAMPT_TRY(attn_t2i(b.Q, b.K, b.V, b.att, F, Nq, Nk, b.part, b.part_floats, s, 128, l.inv));
   else SAMPT_TRY(attn_rowblock(b.Q, b.K, b.V, b.att, F, Nq, Nk, heads, hd, nk_item, s));
   SAMPT_TRY(l.lin(b.att, F * Nq, a.inner, a.ow, a.ob, out, C, ACT_NONE, resid));
   return layernorm_rows(out, lnw, lnb, out, (long)F * Nq, C, 1e-5f, nullptr, 0, ACT_NONE, s);
@@ -308,7 +316,7 @@ int DecEngine::decode(int F, const float* features, const float* hq_feat, const 
   float* skws = ws.f32(skn);
   if (!ws.ok()) return SAMPT_ERR_WORKSPACE;
   if (ws.dry()) return SAMPT_OK;
-  L l{s, skws, skn, w_hl.empty() ? nullptr : &w_hl};
+  L l{s, skws, skn, w_hl.empty() ? nullptr : &w_hl, F, batch_invariant};
 
   // ---- prompt encoder
   SAMPT_TRY(sam_tokens(out_tokens, NO, pts, labels, k, ld_pts, box, gauss, point_emb, not_a_point, (float)c.img, F,
@@ -337,7 +345,7 @@ int DecEngine::decode(int F, const float* features, const float* hq_feat, const 
     SAMPT_TRY(add_bcast(queries, qpe, b.qin, nT, nT, s));
     SAMPT_TRY(fused_proj(l, kvq[i], b.keys, (long)FP, C, P, b.kvq));
     SAMPT_TRY(l.lin(b.qin, (int)FT, C, Ly.t2i.qw, Ly.t2i.qb, b.Q, inner));
-    SAMPT_TRY(attn_t2i(b.Q, b.kvq, b.kvq + inner, b.att, F, Nt, P, b.part, b.part_floats, s, 3 * inner));
+    SAMPT_TRY(attn_t2i(b.Q, b.kvq, b.kvq + inner, b.att, F, Nt, P, b.part, b.part_floats, s, 3 * inner, l.inv));
     SAMPT_TRY(attn_tail(l, Ly.t2i, C, (long)FT, b.att, queries, queries, Ly.n2w, Ly.n2b, s));
     // MLP (ReLU)
     SAMPT_TRY(l.lin(queries, (int)FT, C, Ly.m1w, Ly.m1b, b.hid, c.mlp, ACT_RELU));
@@ -353,7 +361,7 @@ int DecEngine::decode(int F, const float* features, const float* hq_feat, const 
   SAMPT_TRY(add_bcast(queries, qpe, b.qin, nT, nT, s));
   SAMPT_TRY(fused_proj(l, fin_kv, b.keys, (long)FP, C, P, b.kvq));
   SAMPT_TRY(l.lin(b.qin, (int)FT, C, fin.qw, fin.qb, b.Q, inner));
-  SAMPT_TRY(attn_t2i(b.Q, b.kvq, b.kvq + inner, b.att, F, Nt, P, b.part, b.part_floats, s, 2 * inner));
+  SAMPT_TRY(attn_t2i(b.Q, b.kvq, b.kvq + inner, b.att, F, Nt, P, b.part, b.part_floats, s, 2 * inner, l.inv));
   SAMPT_TRY(attn_tail(l, fin, C, (long)FT, b.att, queries, queries, nfw, nfb, s));
 
   // ---- upscaling: ConvT2x2s2 (C -> C/4) + LN2d + GELU ; ConvT2x2s2 (C/4 -> C/8) + GELU   (pixel shuffle via row maps
@@ -488,7 +496,7 @@ int DecEngine::decode_points(int n, const float* features, const float* hq_feat,
   b.Q = ws.f32(FT * C), b.K = ws.f32(FT * C), b.V = ws.f32(FT * C);     // token-side projections only (the image side is kvq)
   b.att = ws.f32(FP * inner > FT * C ? FP * inner : FT * C);
   b.hid = ws.f32(FT * c.mlp);
-  b.part_floats = attn_t2i_workspace_floats(1, (int)FT, P);            // covers (F, Nt) as well: the bound is the same expression
+  b.part_floats = attn_t2i_workspace_floats(1, (int)FT, P);            // covers (F, Nt) as well: the bound only sees F * Nt
   b.part = ws.f32(b.part_floats ? b.part_floats : 4);
   b.up0 = ws.f32(4 * FP * (C / 4));
   b.up1 = ws.f32(16 * FP * (C / 8));
@@ -500,7 +508,7 @@ int DecEngine::decode_points(int n, const float* features, const float* hq_feat,
   float* skws = ws.f32(skn);
   if (!ws.ok()) return SAMPT_ERR_WORKSPACE;
   if (ws.dry()) return SAMPT_OK;
-  L l{s, skws, skn, w_hl.empty() ? nullptr : &w_hl};
+  L l{s, skws, skn, w_hl.empty() ? nullptr : &w_hl, F, batch_invariant};
 
   SAMPT_TRY(sam_tokens(out_tokens, NO, pts, labels, k, k, nullptr, gauss, point_emb, not_a_point, (float)c.img, F, nullptr, nullptr,
                        b.tokens, s));
@@ -520,10 +528,10 @@ int DecEngine::decode_points(int n, const float* features, const float* hq_feat,
     SAMPT_TRY(l.lin(b.qin, (int)FT, C, Ly.t2i.qw, Ly.t2i.qb, b.Q, inner));
     if (i == 0) {      // shared image: P rows projected once, all n * Nt token queries attend to them as one item
       SAMPT_TRY(fused_proj(l, kvq[0], keys0, (long)P, C, P, b.kvq));
-      SAMPT_TRY(attn_t2i(b.Q, b.kvq, b.kvq + inner, b.att, 1, (int)FT, P, b.part, b.part_floats, s, 3 * inner));
+      SAMPT_TRY(attn_t2i(b.Q, b.kvq, b.kvq + inner, b.att, 1, (int)FT, P, b.part, b.part_floats, s, 3 * inner, l.inv));
     } else {
       SAMPT_TRY(fused_proj(l, kvq[i], b.keys, (long)FP, C, P, b.kvq));
-      SAMPT_TRY(attn_t2i(b.Q, b.kvq, b.kvq + inner, b.att, F, Nt, P, b.part, b.part_floats, s, 3 * inner));
+      SAMPT_TRY(attn_t2i(b.Q, b.kvq, b.kvq + inner, b.att, F, Nt, P, b.part, b.part_floats, s, 3 * inner, l.inv));
     }
     SAMPT_TRY(attn_tail(l, Ly.t2i, C, (long)FT, b.att, queries, queries, Ly.n2w, Ly.n2b, s));
     SAMPT_TRY(l.lin(queries, (int)FT, C, Ly.m1w, Ly.m1b, b.hid, c.mlp, ACT_RELU));
@@ -544,7 +552,7 @@ int DecEngine::decode_points(int n, const float* features, const float* hq_feat,
   SAMPT_TRY(add_bcast(queries, qpe, b.qin, nT, nT, s));
   SAMPT_TRY(fused_proj(l, fin_kv, b.keys, (long)FP, C, P, b.kvq));
   SAMPT_TRY(l.lin(b.qin, (int)FT, C, fin.qw, fin.qb, b.Q, inner));
-  SAMPT_TRY(attn_t2i(b.Q, b.kvq, b.kvq + inner, b.att, F, Nt, P, b.part, b.part_floats, s, 2 * inner));
+  SAMPT_TRY(attn_t2i(b.Q, b.kvq, b.kvq + inner, b.att, F, Nt, P, b.part, b.part_floats, s, 2 * inner, l.inv));
   SAMPT_TRY(attn_tail(l, fin, C, (long)FT, b.att, queries, queries, nfw, nfb, s));
 
   SAMPT_TRY(convt_pair(*this, F, b.keys, C, up0_w, up0_b, C / 4, upln_w, upln_b, up1_w, up1_b, C / 8, ACT_GELU, nullptr, b.up0,

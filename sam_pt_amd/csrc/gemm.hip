@@ -307,6 +307,35 @@ __global__ __launch_bounds__(256) void gemm_skinny_f32(GemmP p) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// row-invariant narrow f32 GEMM (GemmP::row_invariant, the shapes the thin kernel's float4 epilogue cannot take: N % 4 != 0,
+// a ldc that is no multiple of 4, K < 64): ONE WAVE PER OUTPUT ELEMENT.  Lane l multiplies k = 4 l + 256 i + {0..3} in order of i,
+// then the wave shuffle sum — the order of C[m][n]'s sum depends on K alone, never on M, N or the element's place in the grid.
+// The decoder's narrow products are its heads' last layers (N = 1 .. 3, K = 256, one row per item): M * N waves of 4 KiB each.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void gemm_rowdot_f32(GemmP p) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long e = (long)blockIdx.x * 4 + wave;
+  if (e >= (long)p.M * p.N) return;            // wave-uniform
+  const int m = (int)(e / p.N), n = (int)(e - (long)m * p.N);
+  const float* a = (const float*)p.A + (long)m * p.lda;
+  const float* w = (const float*)p.W + (long)n * p.ldw;
+  float acc = 0.f;
+  for (int k = lane * 4; k < p.K; k += 256) {
+    const float4 av = *(const float4*)(a + k), wv = *(const float4*)(w + k);
+    acc += av.x * wv.x + av.y * wv.y + av.z * wv.z + av.w * wv.w;
+  }
+  const float sum = wave_sum(acc);
+  if (lane == 0) {
+    float v = sum * p.alpha;
+    if (p.bias) v += p.bias[n];
+    v = apply_act(v, p.act);
+    const int rrow = p.res_mod > 0 ? m % p.res_mod : m;
+    if (p.res) v += p.res[(long)rrow * p.ldr + n];
+    ((float*)p.C)[(long)m * p.ldc + n] = v;
+  }
+}
+
 int gemm_f16_glds_launch(const GemmP& p, hipStream_t s);  // gemm_f16.hip
 
 // tile / split-K selection shared by the dispatcher and gemm_f32_plan_splitk
@@ -332,6 +361,7 @@ static bool thin_f32_eligible(const GemmP& p, bool plain);
 
 int gemm_f32_plan_splitk(const GemmP& p) {
   const bool plain = !p.conv && !p.w_kn && p.nb1 * p.nb2 == 1 && !p.rowmap && !p.a_rowmap;
+  if (plain && p.row_invariant) return 1;   // row-invariant routes: never split over the grid
   if (plain && p.M <= 16) return 1;  // skinny path
   if (thin_f32_eligible(p, plain)) return 1;             // thin path: K is split inside the workgroup
   int BM;
@@ -423,30 +453,84 @@ __global__ __launch_bounds__(NWV * 64) void gemm_thin_f32(GemmP p) {
   }
 }
 
-// the thin kernel takes plain f32 GEMMs whose 64 x 64 tiling would leave most CUs idle (the split-K regime)
-static bool thin_f32_eligible(const GemmP& p, bool plain) {
-  if (!plain || p.out_f16 || p.M <= 16 || p.K < 64) return false;
+// what gemm_thin_f32's float4 loads and stores need of the operands — nothing here looks at M
+static bool thin_f32_operands_ok(const GemmP& p) {
+  if (p.out_f16 || p.K < 64) return false;
   if ((p.N % 4) || (p.ldc % 4) || (p.res && (p.ldr % 4)) || (p.lda % 4) || (p.ldw % 4) || (p.K % 4)) return false;
   if (((uintptr_t)p.C & 15) || (p.bias && ((uintptr_t)p.bias & 15)) || (p.res && ((uintptr_t)p.res & 15))) return false;
+  return true;
+}
+
+// the thin kernel takes plain f32 GEMMs whose 64 x 64 tiling would leave most CUs idle (the split-K regime)
+static bool thin_f32_eligible(const GemmP& p, bool plain) {
+  if (!plain || p.M <= 16 || !thin_f32_operands_ok(p)) return false;
   const long tiles64 = (long)cdiv(p.M, 64) * cdiv(p.N, 64);
   return tiles64 < 128;
 }
 
-int g_thin_min_wgs = 256;    // experiment knob (sampt_gemm_set_thin_min_wgs): see gemm_thin_f32_launch
+int g_thin_min_wgs = 256;    // experiment knob (sampt_gemm_set_thin_min_wgs): see thin_f32_plan
+
+// tile height (FM fragments of 16 rows) and K shares (NWV waves) of a thin launch.  FM only says how many rows share a workgroup:
+// a row's sum is the same for every FM.  NWV IS the order of the sum (the shares are added in wave order); by default it follows
+// FM, so it follows M — under GemmP::row_invariant it is taken from K alone.
+static void thin_f32_plan(const GemmP& p, int& FM, int& NWV) {
+  const long cols = cdiv(p.N, 16);
+  FM = 4;                                      // the tallest tile that still yields >= 256 workgroups (>= 1 per CU)
+  while (FM > 1 && cols * cdiv(p.M, 16 * FM) < g_thin_min_wgs) FM >>= 1;
+  const int nchunk = cdiv(p.K, 16), per_wave = (FM >= 4 && !p.row_invariant) ? 4 : 8;
+  NWV = nchunk > 8 * per_wave ? 16 : (nchunk > 4 * per_wave ? 8 : 4);   // a wave's K share: one batch of loads
+}
 
 static int gemm_thin_f32_launch(const GemmP& p, hipStream_t s) {
-  const long cols = cdiv(p.N, 16);
-  int FM = 4;                                  // the tallest tile that still yields >= 256 workgroups (>= 1 per CU)
-  while (FM > 1 && cols * cdiv(p.M, 16 * FM) < g_thin_min_wgs) FM >>= 1;
-  const int nchunk = cdiv(p.K, 16), per_wave = FM >= 4 ? 4 : 8;
-  int NWV = nchunk > 8 * per_wave ? 16 : (nchunk > 4 * per_wave ? 8 : 4);   // a wave's K share: one batch of loads
-  dim3 grid((unsigned)cols, (unsigned)cdiv(p.M, 16 * FM)), block(NWV * 64);
+  int FM, NWV;
+  thin_f32_plan(p, FM, NWV);
+  const long rows = cdiv(p.M, 16 * FM);
+  if (rows > 65535) return SAMPT_ERR_UNSUPPORTED;
+  dim3 grid((unsigned)cdiv(p.N, 16), (unsigned)rows), block(NWV * 64);
 #define THIN(FMv, NWVv) hipLaunchKernelGGL((gemm_thin_f32<FMv, NWVv>), grid, block, 0, s, p)
   if (FM == 4) { if (NWV == 16) THIN(4, 16); else if (NWV == 8) THIN(4, 8); else THIN(4, 4); }
   else if (FM == 2) { if (NWV == 16) THIN(2, 16); else if (NWV == 8) THIN(2, 8); else THIN(2, 4); }
   else { if (NWV == 16) THIN(1, 16); else if (NWV == 8) THIN(1, 8); else THIN(1, 4); }
 #undef THIN
   SAMPT_CHECK_LAUNCH("gemm_thin_f32");
+  return SAMPT_OK;
+}
+
+// The kernel a plain-or-not f32 product goes to, and the number of K partitions whose sums meet at the end (64 lanes, NWV waves or
+// split-K slices): what gemm_dispatch<float> launches and what gemm_f32_route reports.
+// GemmP::row_invariant (plain products only): the choice looks at K, N, the leading dimensions and the pointers' alignment — never
+// at M — and both kernels it can name sum a row in an order that K alone decides.
+static int plan_route_f32(const GemmP& p, bool plain, int& kparts) {
+  int FM, NWV;
+  if (plain && p.row_invariant) {
+    if (thin_f32_operands_ok(p)) {
+      thin_f32_plan(p, FM, NWV);
+      kparts = NWV;
+      return GEMM_ROUTE_INV_THIN;
+    }
+    kparts = 64;
+    return GEMM_ROUTE_INV_ROWDOT;
+  }
+  if (plain && p.M <= 16) {
+    kparts = 64;
+    return GEMM_ROUTE_SKINNY;
+  }
+  if (thin_f32_eligible(p, plain)) {
+    thin_f32_plan(p, FM, NWV);
+    kparts = NWV;
+    return GEMM_ROUTE_THIN;
+  }
+  int BM;
+  bool big;
+  kparts = plan_tiles_splitk(p, plain, BM, big);
+  return GEMM_ROUTE_TILED;
+}
+
+static bool gemm_is_plain(const GemmP& p) { return !p.conv && !p.w_kn && p.nb1 * p.nb2 == 1 && !p.rowmap && !p.a_rowmap; }
+
+int gemm_f32_route(const GemmP& p, int* route, int* kparts) {
+  if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.K % 4 || !route || !kparts) return SAMPT_ERR_ARG;
+  *route = plan_route_f32(p, gemm_is_plain(p), *kparts);
   return SAMPT_OK;
 }
 
@@ -473,11 +557,13 @@ static int gemm_dispatch(const GemmP& p_in, hipStream_t s) {
   if (((uintptr_t)p.A | (uintptr_t)p.W) & 15) return SAMPT_ERR_ARG;
   if ((p.sA1 | p.sA2 | p.sW1 | p.sW2) % VEC) return SAMPT_ERR_ARG;
   const int batch = p.nb1 * p.nb2;
-  const bool plain = !p.conv && !p.w_kn && batch == 1 && !p.rowmap && !p.a_rowmap;
+  const bool plain = gemm_is_plain(p);
 
-  // ---- skinny path
+  // ---- the latency-bound plain f32 shapes: skinny / thin, or the two row-invariant kernels
   if constexpr (sizeof(T) == 4) {
-    if (plain && p.M <= 16) {
+    int kparts;
+    const int route = plan_route_f32(p, plain, kparts);
+    if (route == GEMM_ROUTE_SKINNY) {
       p.splitk = 1;
       dim3 grid(cdiv(p.N, 8)), block(256);
       if (p.M <= 4) hipLaunchKernelGGL(gemm_skinny_f32<4>, grid, block, 0, s, p);
@@ -485,10 +571,13 @@ static int gemm_dispatch(const GemmP& p_in, hipStream_t s) {
       SAMPT_CHECK_LAUNCH("gemm_skinny");
       return SAMPT_OK;
     }
-  }
-
-  if constexpr (sizeof(T) == 4) {
-    if (thin_f32_eligible(p, plain)) return gemm_thin_f32_launch(p, s);
+    if (route == GEMM_ROUTE_THIN || route == GEMM_ROUTE_INV_THIN) return gemm_thin_f32_launch(p, s);
+    if (route == GEMM_ROUTE_INV_ROWDOT) {
+      p.splitk = 1;
+      hipLaunchKernelGGL(gemm_rowdot_f32, dim3((unsigned)cdiv((long)p.M * p.N, 4)), dim3(256), 0, s, p);
+      SAMPT_CHECK_LAUNCH("gemm_rowdot");
+      return SAMPT_OK;
+    }
   }
 
   // ---- tile selection: the big tile only when it still yields enough workgroups for 256 CUs;

@@ -350,7 +350,10 @@ int attn_rowblock(const float* q, const float* k, const float* v, float* out, in
 // partial softmax states merged by a second launch; ws: attn_t2i_workspace_floats(F, Nq, Nk) floats (0: none needed)
 size_t attn_t2i_workspace_floats(int F, int Nq, int Nk);
 int attn_t2i(const float* q, const float* k, const float* v, float* out, int F, int Nq, int Nk, float* ws, size_t ws_floats,
-             hipStream_t s, int ldkv = 128 /* row stride of k and v in floats (slices of a fused projection) */);
+             hipStream_t s, int ldkv = 128 /* row stride of k and v in floats (slices of a fused projection) */,
+             bool fixed_split = false /* key split from Nk alone: a query's result does not depend on F or Nq */);
+// the key split attn_t2i makes: KS splits of kper keys (host only)
+void attn_t2i_plan_query(int F, int Nq, int Nk, bool fixed_split, int* KS, int* kper);
 int attn_fewkeys(const float* q, const float* k, const float* v, float* out, int F, int Nq, int Nk, int heads, int hd,
                  const int* nk_item, hipStream_t s, int ldq = 0 /* row stride of q in floats (0: heads*hd) */,
                  bool shared_q = false /* q is [Nq][ldq], the same queries for every item (8 heads x 16 channels only) */);

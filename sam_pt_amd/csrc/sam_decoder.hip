@@ -426,10 +426,12 @@ __global__ void k_attn_t2i_merge(const float* __restrict__ part, float* __restri
   *(float4*)(out + row * 128 + c4 * 4) = make_float4(a.x / st, a.y / st, a.z / st, a.w / st);
 }
 
-// key split: enough workgroups to fill the chip (>= ~512), at least 64 keys each, at most 32 splits
-static void attn_t2i_plan(int F, int Nq, int Nk, int& qblocks, int& KS, int& kper) {
+// key split: enough workgroups to fill the chip (>= ~512), at least 64 keys each, at most 32 splits.
+// fixed_split (the decoder's batch-invariant mode): the split a launch of ONE workgroup row (F * qblocks == 1) gets — KS and kper
+// are then functions of Nk alone, so a query merges the same partial softmax states whatever shares its launch.
+static void attn_t2i_plan(int F, int Nq, int Nk, bool fixed_split, int& qblocks, int& KS, int& kper) {
   qblocks = cdiv(Nq, T2I_NQ);
-  const long wg = (long)F * qblocks;
+  const long wg = fixed_split ? 1 : (long)F * qblocks;
   int want = (int)((512 + wg - 1) / wg);
   want = want < 1 ? 1 : (want > 32 ? 32 : want);
   const int most = Nk / 64 > 0 ? Nk / 64 : 1;
@@ -438,18 +440,26 @@ static void attn_t2i_plan(int F, int Nq, int Nk, int& qblocks, int& KS, int& kpe
   KS = cdiv(Nk, kper);
 }
 
+void attn_t2i_plan_query(int F, int Nq, int Nk, bool fixed_split, int* KS, int* kper) {
+  int qb;
+  attn_t2i_plan(F, Nq, Nk, fixed_split, qb, *KS, *kper);
+}
+
 size_t attn_t2i_workspace_floats(int F, int Nq, int Nk) {
-  // F * Nq * KS records with KS <= 512 / (F * qblocks) + 1 and Nq / qblocks <= T2I_NQ: a bound that grows with F and Nq,
-  // so a workspace sized for the largest batch / prompt also covers every smaller one
-  (void)Nk;
-  return ((size_t)512 * T2I_NQ + (size_t)F * Nq) * T2I_REC;
+  // default split: F * Nq * KS records with KS <= 512 / (F * qblocks) + 1 and Nq / qblocks <= T2I_NQ: a bound that grows with F
+  // and Nq, so a workspace sized for the largest batch / prompt also covers every smaller one.
+  // fixed split: KS does not shrink as F grows — F * Nq * KS(Nk) records.  The size returned holds for both.
+  int qb, KS, kper;
+  attn_t2i_plan(1, 1, Nk, true, qb, KS, kper);
+  const size_t dflt = (size_t)512 * T2I_NQ + (size_t)F * Nq, fixed = (size_t)F * Nq * KS;
+  return (dflt > fixed ? dflt : fixed) * T2I_REC;
 }
 
 int attn_t2i(const float* q, const float* k, const float* v, float* out, int F, int Nq, int Nk, float* ws, size_t ws_floats,
-             hipStream_t s, int ldkv) {
+             hipStream_t s, int ldkv, bool fixed_split) {
   if (Nk <= 0 || Nq <= 0 || F <= 0 || ldkv < 128 || ldkv % 4 || (long)Nk * ldkv * 4 >= (1L << 32)) return SAMPT_ERR_ARG;
   int qb, KS, kper;
-  attn_t2i_plan(F, Nq, Nk, qb, KS, kper);
+  attn_t2i_plan(F, Nq, Nk, fixed_split, qb, KS, kper);
   if (KS > 1 && (!ws || ws_floats < (size_t)F * Nq * KS * T2I_REC)) return SAMPT_ERR_WORKSPACE;
   hipLaunchKernelGGL(k_attn_t2i_part, dim3(KS, qb, F), dim3(256), 0, s, q, k, v, ws, out, Nq, Nk, kper, ldkv);
   SAMPT_CHECK_LAUNCH("attn_t2i_part");

@@ -150,7 +150,8 @@ class SamHip(nn.Module):
     def __init__(self, variant: Optional[str] = None, checkpoint: Optional[str] = None, state_dict=None, seed: int = 72,
                  precision: str = "f16", config: Optional[SamConfig] = None, max_batch: int = 8,
                  max_decode_batch: int = 128, hq: Optional[bool] = None, image_encoder=None, prompt_encoder=None,
-                 mask_decoder=None, pixel_mean=None, pixel_std=None, clip_decode_batch: Optional[int] = None, **hydra_kwargs):
+                 mask_decoder=None, pixel_mean=None, pixel_std=None, clip_decode_batch: Optional[int] = None,
+                 batch_invariant_decode: bool = False, **hydra_kwargs):
         """``hq``: build the HQ-SAM decoder (sam_pt/modeling/sam.py SamHQHydra, configs/model/sam/samhq_vit_*.yaml);
         default: inferred from the checkpoint (presence of ``mask_decoder.hf_token.weight``) or from the ``mask_decoder``
         node's ``_target_`` (``...MaskDecoderHQ``).
@@ -173,7 +174,14 @@ class SamHip(nn.Module):
         ``clip_decode_batch``: items per decoder chain of ``SamPt``'s fused clip path.  None leaves it at ``max_decode_batch`` for a
         ViT encoder and makes it 1 for a TinyViT one: the decoder's f32 GEMMs choose their kernel by row count, so only a chain of
         one item sums in the order of a ``predict_torch`` call, and this encoder's clip path is held to the per-frame path bit for
-        bit.  A larger value batches the chains again, at a difference of a few 1e-7 in the logits."""
+        bit.  A larger value batches the chains again, at a difference of a few 1e-7 in the logits.
+
+        ``batch_invariant_decode``: run the mask decoder in its batch-invariant mode (``sampt_dec_set_batch_invariant``): every
+        item of a decoder chain, of a ``predict_points_batch`` chunk or of ``SamPtInteractive``'s batched chains gets the bits it
+        gets in a call of its own, so ``SamPt.forward`` equals ``set_image`` / ``predict_torch`` bit for bit at any chain length,
+        for ViT and TinyViT encoders alike.  With it ``clip_decode_batch=None`` means ``max_decode_batch`` for a TinyViT predictor
+        too (an explicit value is still honoured).  The mode's results differ from the default's by rounding; its price is
+        measured in profiles/batch_invariant_bench.log."""
         super().__init__()
         if config is None:
             config = self._config_from_hydra(image_encoder, mask_decoder, pixel_mean, pixel_std, hydra_kwargs)
@@ -202,8 +210,9 @@ class SamHip(nn.Module):
         self.precision = precision
         self.max_batch = max_batch
         self.max_decode_batch = max_decode_batch
+        self.batch_invariant_decode = bool(batch_invariant_decode)
         if clip_decode_batch is None and isinstance(self.cfg, TinyVitConfig):
-            clip_decode_batch = 1
+            clip_decode_batch = max_decode_batch if self.batch_invariant_decode else 1
         if clip_decode_batch is not None and not 1 <= int(clip_decode_batch) <= max_decode_batch:
             raise ValueError(f"clip_decode_batch={clip_decode_batch} must lie in 1..max_decode_batch ({max_decode_batch})")
         self.clip_decode_batch = clip_decode_batch          # None: SamPt chunks its clip chains by max_decode_batch
@@ -383,9 +392,19 @@ class SamPredictor(_lib.EngineOwner):
         for i in range(3):
             c.pixel_mean[i], c.pixel_std[i] = cfg.pixel_mean[i], cfg.pixel_std[i]
         self._vit = _lib.create_engine(lib, "sampt_tinyvit_create", self._wv, m.max_batch, pre=(C.byref(c),))
+        return self._vit, self._build_decoder(lib, dev)
+
+    def _build_decoder(self, lib, dev):
+        cfg, m = self.model.cfg, self.model
         self._wd = pack_decoder(m.sd, cfg, dev, m.max_decode_batch, hq=m.hq)
-        return self._vit, _lib.create_engine(lib, "sampt_dec_create", self._wd, cfg.grid, cfg.img_size, m.max_decode_batch,
-                                             cfg.hq_dim if m.hq else 0)
+        dec = _lib.create_engine(lib, "sampt_dec_create", self._wd, cfg.grid, cfg.img_size, m.max_decode_batch,
+                                 cfg.hq_dim if m.hq else 0)
+        if getattr(m, "batch_invariant_decode", False):      # (a new handle has the mode off: nothing to call otherwise)
+            rc = lib.sampt_dec_set_batch_invariant(dec, 1)
+            if rc != 0:
+                lib.sampt_dec_destroy(dec)
+                _lib.check(rc, "sampt_dec_set_batch_invariant")
+        return dec
 
     def _build(self, lib, dev):
         if self._tiny:
@@ -402,9 +421,15 @@ class SamPredictor(_lib.EngineOwner):
             c.pixel_mean[i], c.pixel_std[i] = cfg.pixel_mean[i], cfg.pixel_std[i]
         # (the encoder's handle is stored at once: should the decoder fail to build, ``__del__`` or the next ``_ensure`` destroys it)
         self._vit = _lib.create_engine(lib, "sampt_vit_create", self._wv, m.max_batch, pre=(C.byref(c),))
-        self._wd = pack_decoder(m.sd, cfg, dev, m.max_decode_batch, hq=m.hq)
-        return self._vit, _lib.create_engine(lib, "sampt_dec_create", self._wd, cfg.grid, cfg.img_size, m.max_decode_batch,
-                                             cfg.hq_dim if m.hq else 0)
+        return self._vit, self._build_decoder(lib, dev)
+
+    @_lib.on_device(lambda self, *a, **k: self.model.device)
+    def set_batch_invariant_decode(self, on: bool) -> None:
+        """Switch the decoder engine's batch-invariant mode (``SamHip(batch_invariant_decode=...)``) on a live predictor, for A / B
+        runs over one set of weights.  ``model.clip_decode_batch`` keeps the value the constructor gave it."""
+        self._ensure()
+        _lib.check(self._lib.sampt_dec_set_batch_invariant(self._dec, 1 if on else 0), "sampt_dec_set_batch_invariant")
+        self.model.batch_invariant_decode = bool(on)
 
     @_lib.on_device(lambda self, *a, **k: self.model.device)
     def set_gemm_workgroups(self, per_xcd):
