@@ -362,6 +362,10 @@ int sampt_vit_set_gemm_workgroups(sampt_vit_t h, int per_xcd);
  * sampt_vit_set_gemm_workgroups says.  The four shapes have different tile counts (N / 256 = 15, 5, 20, 5 column tiles for
  * ViT-H), so the number of workgroups that wastes least of the last round of tiles differs per kind. */
 int sampt_vit_set_gemm_workgroups_kind(sampt_vit_t h, int qkv, int proj, int fc1, int fc2);
+/* Per handle, fp16 mode (cfg.f16 == 1; ignored by the other two): on = 1 (default) — the qkv GEMM of every block writes the head-major
+ * matrix [3][heads][rows][hd] and the attention kernel reads it (sampt_gemm_f16_head_major, sampt_vit_attention_f16_head_major)
+ * instead of token-major rows.  Bitwise the same embeddings.  A new handle has it ON (the measured default: DESIGN.md section 4, k_flash_f16); 0 = token-major. */
+int sampt_vit_set_attention_head_major(sampt_vit_t h, int on);
 /* Process-wide experiment knob of the 8-phase fp16 GEMM (csrc/gemm_f16_p8.hip): G > 1 phase groups — persistent workgroup w of an
  * XCD belongs to group w % G and starts (w % G) / G of a tile's K-loop late, so that the groups' epilogue bursts interleave with
  * the other groups' K-loops.  0 / 1 = off (the default). */
@@ -986,6 +990,19 @@ int sampt_cotracker_attention_f32(const float* qkv_dev, float* out_dev, int nbat
  * are unused (kept for ABI stability: K / V tiles are staged by LDS-DMA, nothing goes through HBM scratch). */
 int sampt_vit_attention_f16(const void* qkv_dev, const float* rel_h_dev, const float* rel_w_dev, void* out_dev, int B,
                             int S, int heads, int hd, void* workspace_dev, size_t workspace_bytes, sampt_stream_t stream);
+/* The same attention from the HEAD-MAJOR fp16 qkv matrix [3][heads][B*S*S][hd] (what sampt_gemm_f16_head_major writes with
+ * rows = B*S*S): the K / V rows of one (window | frame, head) are one contiguous run, a key tile is a linear copy.  bias_row_dev
+ * non-null: the B = frames * nwx * nwy launches are SAM's windows as in sampt_vit_window_attention (bias_row_dev: the qkv bias as
+ * ONE TOKEN-MAJOR row of 3*heads*hd halves); null: whole frames, nwx .. grid_w ignored.  out fp16 token-major [B*S*S][heads*hd],
+ * bitwise what sampt_vit_attention_f16 / sampt_vit_window_attention(precision 1) give on the token-major rows of the same values. */
+int sampt_vit_attention_f16_head_major(const void* qkv_dev, const float* rel_h_dev, const float* rel_w_dev, void* out_dev, int B,
+                                       int S, int heads, int hd, const void* bias_row_dev, int nwx, int nwy, int grid_h, int grid_w,
+                                       sampt_stream_t stream);
+/* fp16 product with the head-major destination: C[((part * heads + h) * rows + r) * hd + c] = A[m] . W[part * heads * hd + h * hd + c]
+ * + bias, r = rowmap_dev[m] (null: m; -1 drops the row), fp32 accumulate, fp16 A [M][K], W [N][K] and C; N % (heads * hd) == 0,
+ * hd % 4 == 0, rows > every destination row.  Element for element the values sampt_gemm_ex(dtype 2) writes to C[r][col]. */
+int sampt_gemm_f16_head_major(const void* A_dev, const void* W_dev, const float* bias_dev, void* C_dev, int M, int N, int K,
+                              int heads, int hd, int rows, const int32_t* rowmap_dev, sampt_stream_t stream);
 /* K-medoids query-point selection (SamPt in query_masks mode / point re-initialisation: sam_pt/utils/query_points.py:62-99,
  * third-party sklearn_extra KMedoids(method="alternate", init="heuristic") restated in sam_pt_amd/query_points.py) on the
  * device, bit-identical to that host restatement: fp64 distances, numpy's pairwise summation order, first-index ties.

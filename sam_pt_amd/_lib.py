@@ -196,6 +196,7 @@ _SIGS = {
                                      _P, _P, _P, c_size_t, _P, C.POINTER(c_int)]),
     "sampt_vit_set_gemm_workgroups": (c_int, [_P, c_int]),
     "sampt_vit_set_gemm_workgroups_kind": (c_int, [_P, c_int, c_int, c_int, c_int]),
+    "sampt_vit_set_attention_head_major": (c_int, [_P, c_int]),
     "sampt_vit_calibrate": (c_int, [_P, _P, c_int]),
     "sampt_gemm_set_stagger": (c_int, [c_int]),
     "sampt_gemm_set_schedule": (c_int, [c_int]),
@@ -252,6 +253,8 @@ _SIGS = {
     "sampt_attention_f32": (c_int, [c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "sampt_cotracker_attention_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "sampt_vit_attention_f16": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "sampt_vit_attention_f16_head_major": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P]),
+    "sampt_gemm_f16_head_major": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "sampt_vit_attention_x3": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "sampt_split_rows_x3": (c_int, [_P, _P, c_int, c_int, _P]),
     "sampt_vit_window_attention": (c_int, [c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P]),

@@ -123,7 +123,14 @@ __device__ half_t g_flash_pad[16] = {(half_t)1.f, (half_t)0.f, (half_t)0.f, (hal
                                      (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f,
                                      (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
 
-template <int HD, int NW, int SG>
+//
+// HM (FlashPad::head_major): q / k / v are read from the head-major matrix [3][heads][B * N][HD] the qkv GEMM writes with
+// GemmP::hm_hd instead of from token-major rows [B * N][3 D].  The K rows of a (frame | window, head) are then ONE run of N * HD * 2
+// bytes (V likewise): a key tile is a linear copy, every 4-lane group of a DMA instruction asks for 64 contiguous, 64-byte aligned
+// bytes (the XOR swizzles permute chunks inside a 32-byte pair only) and a K tile touches 80 128-byte lines instead of 128.  Only
+// the source addresses differ: which slots are clamped, padded from the bias row (a token-major row in both modes) or taken from
+// the pad page, the LDS image, the arithmetic and the token-major output are the same, bit for bit.
+template <int HD, int NW, int SG, bool HM>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 2) void k_flash_f16(const half_t* __restrict__ qkv, const float* __restrict__ rel_h,
                                                        const float* __restrict__ rel_w, half_t* __restrict__ out, int N,
                                                        int heads, float scale, FlashPad pad, int B, int uh) {
@@ -170,6 +177,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 2) void k_flash_f16(const ha
   flash_wg_decode(blockIdx.x, (N + QT - 1) / QT, heads, B, uh, bx, h, b);
   const int D = heads * HD;
   const long tok0 = (long)b * N;
+  const long hrows = (long)B * N;                       // HM: rows of one head's block
   const int qblk = bx * QT;
   const int ql = wave * 32 + li;
   const int q = qblk + ql;
@@ -218,11 +226,11 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 2) void k_flash_f16(const ha
   }
   // kt0 / kh0: first key / first grid row of the tile
   auto dma_tile = [&](int kt0, int kh0, int buf) {
-    const half_t* kbase = qkv + tok0 * 3 * D + D + h * HD;
+    const half_t* kbase = HM ? qkv + ((long)(heads + h) * hrows + tok0) * HD : qkv + tok0 * 3 * D + D + h * HD;
     // (32-bit row offsets: one (frame | window) of qkv rows is far below 4 GB; tok0 is part of the 64-bit base)
-    const unsigned stride = 3u * (unsigned)D * 2u;
+    const unsigned stride = HM ? (unsigned)HD * 2u : 3u * (unsigned)D * 2u;   // HM: a compile-time constant, rows back to back
     const char* kb = (const char*)kbase;
-    const char* vb = (const char*)(kbase + D);
+    const char* vb = (const char*)(HM ? kbase + (long)heads * hrows * HD : kbase + D);
     const char* pk = (const char*)(pad.bias_row ? pad.bias_row + D + h * HD : kbase);
     const char* pv = (const char*)(pad.bias_row ? pad.bias_row + 2 * D + h * HD : kbase);
     int n = 0;
@@ -262,7 +270,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 2) void k_flash_f16(const ha
   h8 qf[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
-    if (q < N && !is_pad(q)) qf[ks] = *(const h8*)(qkv + (tok0 + q) * 3 * D + h * HD + ks * 16 + hi * 8);
+    if (q < N && !is_pad(q))
+      qf[ks] = *(const h8*)(HM ? qkv + ((long)h * hrows + tok0 + q) * HD + ks * 16 + hi * 8
+                               : qkv + (tok0 + q) * 3 * D + h * HD + ks * 16 + hi * 8);
     else qf[ks] = (h8){0, 0, 0, 0, 0, 0, 0, 0};
   }
   __syncthreads();
@@ -477,9 +487,14 @@ int vit_flash_attention_f16(const half_t* qkv, const float* relh, const float* r
   const float scale = 1.0f / sqrtf((float)hd);
   // work order: windows are kept whole on one XCD (common.h flash_wg_decode); global blocks keep the plain order (grouping the
   // 32 query blocks of a (frame, head) per XCD measured 0.7 % slower, profiles/r4_c16_*)
-#define FL(HDv, NWv, SGv)                                                                                     \
-  hipLaunchKernelGGL((k_flash_f16<HDv, NWv, SGv>), dim3(cdiv(N, NWv * 32) * heads * B), dim3(NWv * 64), 0, s, qkv, relh, relw, \
+#define FL1(HDv, NWv, SGv, HMv)                                                                                  \
+  hipLaunchKernelGGL((k_flash_f16<HDv, NWv, SGv, HMv>), dim3(cdiv(N, NWv * 32) * heads * B), dim3(NWv * 64), 0, s, qkv, relh, relw, \
                      out, N, heads, scale, pad, B, SGv < 64 ? heads : 0)
+#define FL(HDv, NWv, SGv)                 \
+  do {                                    \
+    if (pad.head_major) FL1(HDv, NWv, SGv, true); \
+    else FL1(HDv, NWv, SGv, false);       \
+  } while (0)
   // (round 6, profiles/r6_c10_*: more queries per workgroup — so that a (frame, head)'s K / V tiles are staged fewer times — LOSES
   //  for the global blocks too: 6 waves / 192 queries 1607 us, 8 waves / 256 queries 1304 us against 1064 us per 8 frames with 4;
   //  7-wave windows 269 vs 210 us.  Resident workgroups, not staged bytes, are what these kernels run on.)
@@ -495,6 +510,7 @@ int vit_flash_attention_f16(const half_t* qkv, const float* relh, const float* r
   else if (S == 6 && hd == 32) FL(32, 2, 6);
   else return SAMPT_ERR_UNSUPPORTED;
 #undef FL
+#undef FL1
   SAMPT_CHECK_LAUNCH("vit_flash_attention_f16");
   return SAMPT_OK;
 }

@@ -356,6 +356,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_flash_x3(const half_t* __restric
 int vit_flash_attention_x3(const half_t* qkv, const float* relh, const float* relw, half_t* out, int B, int S, int heads,
                            int hd, hipStream_t s, FlashPad pad) {
   if (pad.bias_row && (pad.nwx <= 0 || pad.nwin <= 0 || B % pad.nwin)) return SAMPT_ERR_ARG;
+  if (pad.head_major) return SAMPT_ERR_UNSUPPORTED;   // x3 rows are token-major only
   const int N = S * S;
   const float scale = 1.0f / sqrtf((float)hd);
   if ((heads * hd) % 32) return SAMPT_ERR_UNSUPPORTED;

@@ -302,6 +302,12 @@ int sampt_vit_set_gemm_workgroups_kind(sampt_vit_t h, int qkv, int proj, int fc1
   return SAMPT_OK;
 }
 
+int sampt_vit_set_attention_head_major(sampt_vit_t h, int on) {
+  if (!h || (on != 0 && on != 1)) return fail(SAMPT_ERR_ARG, "sampt_vit_set_attention_head_major: need a handle and on = 0 | 1");
+  h->e.attn_head_major = on;
+  return SAMPT_OK;
+}
+
 int sampt_gemm_set_schedule(int sched) {
   if (sched < 0 || sched > 1) return fail(SAMPT_ERR_ARG, "sampt_gemm_set_schedule: 0 or 1");
   sampt::g_p8_sched = sched;
@@ -1792,6 +1798,26 @@ int sampt_vit_attention_f16(const void* qkv, const float* rel_h, const float* re
                             int hd, void* ws, size_t ws_bytes, sampt_stream_t stream) {
   (void)ws, (void)ws_bytes;  // the decomposed rel-pos bias is computed inside the kernel: no scratch needed any more
   return vit_flash_attention_f16((const half_t*)qkv, rel_h, rel_w, (half_t*)out, B, S, heads, hd, (hipStream_t)stream);
+}
+
+int sampt_vit_attention_f16_head_major(const void* qkv, const float* rel_h, const float* rel_w, void* out, int B, int S, int heads,
+                                       int hd, const void* bias_row, int nwx, int nwy, int grid_h, int grid_w, sampt_stream_t stream) {
+  if (!qkv || !rel_h || !rel_w || !out || B <= 0 || (bias_row && (nwx <= 0 || nwy <= 0 || B % (nwx * nwy))))
+    return fail(SAMPT_ERR_ARG, "sampt_vit_attention_f16_head_major: bad arguments");
+  FlashPad fp;
+  fp.head_major = 1;
+  if (bias_row) fp.bias_row = (const half_t*)bias_row, fp.nwx = nwx, fp.nwin = nwx * nwy, fp.gh = grid_h, fp.gw = grid_w;
+  return vit_flash_attention_f16((const half_t*)qkv, rel_h, rel_w, (half_t*)out, B, S, heads, hd, (hipStream_t)stream, fp);
+}
+
+int sampt_gemm_f16_head_major(const void* A, const void* W, const float* bias, void* C, int M, int N, int K, int heads, int hd,
+                              int rows, const int32_t* rowmap, sampt_stream_t stream) {
+  if (!A || !W || !C || heads <= 0 || hd <= 0 || rows <= 0) return fail(SAMPT_ERR_ARG, "sampt_gemm_f16_head_major: bad arguments");
+  GemmP p = gemm_linear(A, K, W, bias, C, N, M, N, K);
+  p.rowmap = rowmap, p.out_f16 = 1, p.hm_heads = heads, p.hm_hd = hd, p.hm_rows = rows;
+  int rc = gemm_f16(p, (hipStream_t)stream);
+  return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_gemm_f16_head_major: need hd % 4 == 0, N % (heads * hd) == 0, rows >= M without a rowmap")
+                             : rc;
 }
 
 int sampt_vit_attention_x3(const void* qkv, const float* rel_h, const float* rel_w, void* out, int B, int S, int heads,

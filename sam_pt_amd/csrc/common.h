@@ -183,6 +183,11 @@ struct GemmP {
   int shuf_g = 0, shuf_n = 0;
   int act = ACT_NONE;
   int out_f16 = 0;               // half inputs only: 1 = C is half; 2 = C is half in the split "x3 row" format (see x3), ldc = 2N
+  // out_f16 == 1 only — head-major destination (the qkv GEMM feeding vit_flash_attention_f16's head-major source): with
+  // D = hm_heads * hm_hd, column col = part * D + h * hm_hd + c of destination row r (after rowmap) goes to
+  // C[((part * hm_heads + h) * hm_rows + r) * hm_hd + c] — layout [part][head][row][hd], hm_rows = rows of the destination
+  // (>= max(rowmap) + 1), the same number of halves as the token-major matrix.  hm_hd % 4 == 0, N % D == 0.  hm_hd = 0: off
+  int hm_hd = 0, hm_heads = 0, hm_rows = 0;
   // x3 (half inputs only): fp32-grade products on the fp16 matrix pipe.  Both operands are "x3 rows": every block of 32
   // consecutive k of a row is stored as 64 halves [hi(32) | lo(32)] with v = hi + lo (hi = fp16(v), lo = fp16(v - hi);
   // weights pre-scaled by 2^F16X3_WSHIFT, the caller passes alpha = 2^-F16X3_WSHIFT).  K / lda / ldw count STORED halves
@@ -223,6 +228,13 @@ struct GemmP {
   float epi_eps = 0.f;
   int epi_ld = 0;
 };
+
+// GemmP::hm_hd > 0: element offset of the head-major column term — everything of the destination that does not depend on the
+// row: ((part * heads + h) * rows) * hd + c.  The row adds r * hd.
+__device__ __forceinline__ long hm_col_term(const GemmP& p, int col) {
+  const int hh = col / p.hm_hd;          // part * heads + h
+  return (long)hh * p.hm_rows * p.hm_hd + (col - hh * p.hm_hd);
+}
 
 extern int g_p8_sched;     // gemm_f16_p8.hip: 0 = stage in the read segments (default), 1 = the round-3 schedule (sampt_gemm_set_schedule)
 extern int g_p8_stagger;

@@ -282,6 +282,10 @@ struct VitEngine {
   // per launch kind (0 qkv, 1 proj, 2 fc1, 3 fc2): overrides gemm_wgs when > 0 (tile counts of the four shapes quantise
   // differently on a given number of workgroups: sampt_vit_set_gemm_workgroups_kind)
   int gemm_wgs_kind[4] = {0, 0, 0, 0};
+  // fp16 mode: the qkv GEMM writes, and the attention kernel reads, the head-major matrix [3][heads][rows][hd] instead of
+  // token-major rows (GemmP::hm_hd, FlashPad::head_major; sampt_vit_set_attention_head_major: 0 = token-major).  Bitwise the same
+  // results; the default by measurement (k_flash_f16).
+  int attn_head_major = 1;
   // Calibration of the fp16 mode's static bias correction (sampt_vit_calibrate): while set, every block GEMM of encode() also
   // writes the column means of its A operand (over the real tokens) to calib[(block * 4 + kind) * calib_ld + k].
   float* calib = nullptr;

@@ -80,9 +80,10 @@ struct G {
   // M, N, K are the logical sizes; in mode 2 A and W are x3 rows (2K halves per row).
   int run(const void* A, int M, int K, const void* W, const float* bias, void* C, int N, int act, int out,
           const float* res, int ldr, const int* rowmap, int res_mod, const int* a_rowmap = nullptr,
-          bool exact = false, const half_t* hl = nullptr, int kind = -1) const {
+          bool exact = false, const half_t* hl = nullptr, int kind = -1, long hm_rows = 0) const {
     GemmP p = gemm_linear(A, K, W, bias, C, N, M, N, K, act, res, ldr, res_mod);
     p.rowmap = rowmap, p.a_rowmap = a_rowmap, p.out_f16 = out;
+    if (hm_rows > 0) p.hm_heads = eng->c.heads, p.hm_hd = eng->c.D / eng->c.heads, p.hm_rows = (int)hm_rows;   // head-major C
     p.p8_wgs = eng ? (kind >= 0 && eng->gemm_wgs_kind[kind] > 0 ? eng->gemm_wgs_kind[kind] : eng->gemm_wgs) : 0;
     if (exact && hl) {   // fp32-grade on the fp16 pipe: the GEMM as a 1x1 convolution over an [1][M][1][K] image
       gemm_split_planes(p, hl);
@@ -223,7 +224,11 @@ int VitEngine::encode(const uint8_t* frames, int chw, int B, int H, int W, float
     // norm1; the window partition (zero padding AFTER the norm, App. A-3) is a row scatter of the qkv GEMM: only the
     // real tokens go through the GEMM, the padded rows' qkv is the bias alone
     SAMPT_TRY(layernorm_rows(x, b.ln1w, b.ln1b, xn, Mg, D, 1e-6f, nullptr, c.f16, ACT_NONE, s));
-    SAMPT_TRY(gm.run(xn, (int)Mg, D, b.qkv_w, b.qkv_b, qkv, 3 * D, ACT_NONE, act_out, nullptr, 0, inv, 0, nullptr, false, nullptr, 0));
+    // (attn_head_major, fp16 mode: the qkv matrix is written as [3][heads][M][hd] — the attention kernel's K / V tiles are then
+    //  linear copies; same values, same results)
+    const bool hm = c.f16 == 1 && attn_head_major;
+    SAMPT_TRY(gm.run(xn, (int)Mg, D, b.qkv_w, b.qkv_b, qkv, 3 * D, ACT_NONE, act_out, nullptr, 0, inv, 0, nullptr, false, nullptr, 0,
+                     hm ? M : 0));
     // the 16-bit attention kernels take the padded tokens' K / V from the bias row themselves (FlashPad); only the exact mode's
     // materialised path needs the padded qkv rows written
     FlashPad fp;
@@ -233,7 +238,7 @@ int VitEngine::encode(const uint8_t* frames, int chw, int B, int H, int W, float
       SAMPT_TRY(fill_rows_bias(qkv, 0, win_pad, (int)(M - Mg), b.qkv_b, 3 * D, s));
     }
     if (c.f16 == 1) {
-      fp.rel_ops = b.rel_ops;
+      fp.rel_ops = b.rel_ops, fp.head_major = hm;
       SAMPT_TRY(vit_flash_attention_f16((const half_t*)qkv, b.rel_h, b.rel_w, (half_t*)att, Bw, S, c.heads, hd, s, fp));
     } else if (c.f16 == 2) {
       SAMPT_TRY(vit_flash_attention_x3((const half_t*)qkv, b.rel_h, b.rel_w, (half_t*)att, Bw, S, c.heads, hd, s, fp));

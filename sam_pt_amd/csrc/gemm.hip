@@ -240,6 +240,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
           split_f16(v, hi, lo);
           half_t* cp = (half_t*)p.C + c_off + (long)drow * p.ldc + x3_col(col);
           cp[0] = hi, cp[32] = lo;
+        } else if (sizeof(T) == 2 && p.out_f16 && p.hm_hd > 0) {   // head-major (GemmP::hm_hd)
+          ((half_t*)p.C)[c_off + (long)drow * p.hm_hd + hm_col_term(p, col)] = (half_t)v;
         } else if (sizeof(T) == 2 && p.out_f16) ((half_t*)p.C)[c_off + (long)drow * p.ldc + col] = (half_t)v;
         else ((float*)p.C)[c_off + (long)drow * p.ldc + col] = v;
       }
@@ -538,6 +540,13 @@ template <typename T>
 static int gemm_dispatch(const GemmP& p_in, hipStream_t s) {
   constexpr int VEC = GT<T>::VEC;
   GemmP p = p_in;
+  // head-major destination (GemmP::hm_hd): plain fp16 output of a plain product only.  With a rowmap the caller vouches for
+  // hm_rows > every destination row (the map lives on the device): a larger row would land in the NEXT head's block, inside C
+  if (p.hm_hd != 0) {
+    if (sizeof(T) != 2 || p.out_f16 != 1 || p.x3 || p.conv || p.nb1 * p.nb2 != 1 || p.hm_hd < 4 || p.hm_hd % 4 || p.hm_heads <= 0 ||
+        p.N % (p.hm_heads * p.hm_hd) || p.hm_rows < (p.rowmap ? 1 : p.M))
+      return SAMPT_ERR_ARG;
+  }
   if constexpr (sizeof(T) == 2) {
     if (!p.force_generic) {
       int rc = gemm_f16_glds_launch(p, s);  // LDS-DMA kernel for the big ViT GEMMs

@@ -206,7 +206,8 @@ __global__ __launch_bounds__((BM / WTM) * (BN / WTN) * 64, 4) void gemm_f16_glds
         *(h4*)(cp + 32) = lo;
       } else if (p.out_f16) {
         h4 o = (h4){(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
-        *(h4*)((half_t*)p.C + (long)drow * p.ldc + col) = o;
+        if (p.hm_hd > 0) *(h4*)((half_t*)p.C + (long)drow * p.hm_hd + hm_col_term(p, col)) = o;   // head-major (GemmP::hm_hd)
+        else *(h4*)((half_t*)p.C + (long)drow * p.ldc + col) = o;
       } else {
         // fp32 C (64-byte row segments per store group) is streamed out non-temporally: +3..8 % on the proj / fc2 shapes;
         // the 32-byte segments of fp16 C need the L2's write combining and lose with it (measured both ways)

@@ -74,6 +74,9 @@ struct FlashPad {
   // [2][ceil((2 S - 1) / 32)][hd / 16][64][8] halves) — the prologue then loads 16 bytes per lane and k-step instead of converting
   // the f32 tables in every workgroup.  Same halves, same results.
   const half_t* rel_ops = nullptr;
+  // vit_flash_attention_f16 only: qkv is the head-major matrix [3][heads][B * S * S][hd] (GemmP::hm_hd with hm_rows = B * S * S)
+  // instead of token-major rows.  bias_row stays a token-major row of 3 D halves; the output stays token-major.  Same results.
+  int head_major = 0;
 };
 // Fused flash-style attention, f16 operands, fp32 softmax/accumulate.  qkv f16 [B*S*S][3*D]; out f16 [B*S*S][D];
 // rel_h / rel_w: rel_pos tables f32 [2S-1][hd] (the decomposed bias is computed inside the kernel).

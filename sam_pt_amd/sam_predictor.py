@@ -342,6 +342,9 @@ class SamPredictor(_lib.EngineOwner):
         # skip the frame-independent padding rows of landscape frames in the blocks before the first global one (exact)
         self.skip_dead_rows = os.environ.get("SAMPT_VIT_SKIP_DEAD", "1") != "0" and not self._tiny
         self._dead_cache = {}
+        # fp16 ViT mode: head-major qkv between the qkv GEMM and the attention kernel (``set_attention_head_major``; bitwise the
+        # same embeddings); SAMPT_ATTN_HEAD_MAJOR=0|1
+        self.attention_head_major = os.environ.get("SAMPT_ATTN_HEAD_MAJOR", "1") != "0" and not self._tiny
         # fp16 ViT mode: static bias correction of the weight rounding, calibrated once per frame geometry (see
         # ``_select_bias_set``); SAMPT_VIT_BIAS_CORR=0 disables
         self.bias_correction = os.environ.get("SAMPT_VIT_BIAS_CORR", "1") != "0" and not self._tiny
@@ -421,6 +424,8 @@ class SamPredictor(_lib.EngineOwner):
             c.pixel_mean[i], c.pixel_std[i] = cfg.pixel_mean[i], cfg.pixel_std[i]
         # (the encoder's handle is stored at once: should the decoder fail to build, ``__del__`` or the next ``_ensure`` destroys it)
         self._vit = _lib.create_engine(lib, "sampt_vit_create", self._wv, m.max_batch, pre=(C.byref(c),))
+        if not self.attention_head_major:                    # (a new handle has it on)
+            _lib.check(lib.sampt_vit_set_attention_head_major(self._vit, 0), "sampt_vit_set_attention_head_major")
         return self._vit, self._build_decoder(lib, dev)
 
     @_lib.on_device(lambda self, *a, **k: self.model.device)
@@ -444,6 +449,15 @@ class SamPredictor(_lib.EngineOwner):
             return
         _lib.check(self._lib.sampt_vit_set_gemm_workgroups_kind(self._vit, 0, 0, 0, 0), "sampt_vit_set_gemm_workgroups_kind")
         _lib.check(self._lib.sampt_vit_set_gemm_workgroups(self._vit, int(per_xcd)), "sampt_vit_set_gemm_workgroups")
+
+    @_lib.on_device(lambda self, *a, **k: self.model.device)
+    def set_attention_head_major(self, on: bool) -> None:
+        """fp16 mode: the encoder's qkv GEMMs write, and its attention kernels read, the head-major qkv matrix instead of token-major
+        rows for the following ``encode_frames`` calls (sampt_vit_set_attention_head_major, include/sampt_hip.h).  Same bits."""
+        self._vit_only("set_attention_head_major")
+        self._ensure()
+        _lib.check(self._lib.sampt_vit_set_attention_head_major(self._vit, 1 if on else 0), "sampt_vit_set_attention_head_major")
+        self.attention_head_major = bool(on)
 
     @_lib.on_device(lambda self, *a, **k: self.model.device)
     def gemm_profile_begin(self):
