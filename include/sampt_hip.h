@@ -405,7 +405,8 @@ int sampt_conv_stem7x7(const float* x_nhwc4, const float* w, const float* bias, 
 /* 3 x 3 stride-1 pad-1 split-fp16 convolution over pre-split planes (sampt_conv2d_nhwc dtype 4) that ALSO produces the statistics of
  * the InstanceNorm2d that follows it in the tracker's encoder (pips.py:191-287 BasicEncoder: every convolution is followed by
  * norm_fn = "instance"): mean_rstd [n][Cout][2] = (mean, 1 / sqrt(biased var + eps)) of y over H x W, summed from the convolution's
- * registers per 16 x 16 tile (fp32 over 64 pixels, fp64 beyond).  ws: n * ceil(H / 16) * ceil(W / 16) * Cout * 16 bytes. */
+ * registers per 16 x 16 tile (fp32 over 64 pixels, fp64 beyond).  ws: n * ceil(H / 16) * ceil(W / 16) * Cout * 16 bytes, 8-byte aligned
+ * (doubles); x_hl, w_hl, y (bias where given): 16-byte aligned — else SAMPT_ERR_ARG. */
 int sampt_conv3x3_planes_instnorm_stats(const void* x_hl, const void* w_hl, const float* bias, float* y, int n, int H, int W, int Cin,
                                         int Cout, float eps, float* mean_rstd, void* ws, size_t ws_bytes, sampt_stream_t stream);
 /* The mask decoder's image-side projection as an operator: C [M][N] = act(A W^T + bias) + res[row % res_mod (0: row)] with f32 A
@@ -424,7 +425,8 @@ int sampt_gemm_x3_rows(const float* A, const void* w_hl, const float* bias, cons
  *            C [M * 4] holds one float per output pixel (the low-resolution mask logits of predict_masks);
  *   epi = 3 (K = 128, N = 256, shuf_g = 0, act = 0, res [M][256] non-null): C = LayerNorm(res + A W^T + bias) over the row, weights
  *            epi_a / epi_b [256] (transformer.py:145-150: keys = norm4(keys + attn_out)); C may be res (in place).
- * Bit for bit what sampt_gemm_x3_rows followed by sampt_layernorm (D = 64, act 2 / D = 256) / sampt_sam_mask_dot computes. */
+ * Bit for bit what sampt_gemm_x3_rows followed by sampt_layernorm (D = 64, act 2 / D = 256) / sampt_sam_mask_dot computes.
+ * A, w_hl, C (bias, res where given): 16-byte aligned; epi_a / epi_b: floats, non-null where the tail reads them — else SAMPT_ERR_ARG. */
 int sampt_gemm_x3_rows_epi(const float* A, const void* w_hl, const float* bias, const float* res, int res_mod, float* C, int M, int N,
                            int K, int act, int shuf_g, int epi, const float* epi_a, const float* epi_b, float epi_eps, int epi_ld,
                            sampt_stream_t stream);

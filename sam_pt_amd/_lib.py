@@ -291,7 +291,7 @@ def load():
         fn.argtypes = args
     if os.environ.get("SAMPT_GEMM_SCHED"):            # A / B switch of the 8-phase GEMM's stage schedule (sampt_gemm_set_schedule)
         lib.sampt_gemm_set_schedule(int(os.environ["SAMPT_GEMM_SCHED"]))
-    if os.environ.get("SAMPT_PIPS_MIXER") or os.environ.get("SAMPT_PIPS_MIXER_WGS") or os.environ.get("SAMPT_PIPS_MIXER_DIAG"):   # csrc/pips_mixer.hip (A / B runs)
+    if os.environ.get("SAMPT_PIPS_MIXER") or os.environ.get("SAMPT_PIPS_MIXER_WGS"):   # csrc/pips_mixer.hip (A / B runs)
         lib.sampt_pips_set_mixer(int(os.environ.get("SAMPT_PIPS_MIXER", "2")), int(os.environ.get("SAMPT_PIPS_MIXER_WGS", "16")))
     if os.environ.get("SAMPT_GEMM_TRIM"):              # A / B switch of the persistent GEMM's workgroup trimming (sampt_gemm_set_trim)
         lib.sampt_gemm_set_trim(int(os.environ["SAMPT_GEMM_TRIM"]))

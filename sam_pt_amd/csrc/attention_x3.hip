@@ -14,6 +14,7 @@
 // Softmax statistics, rescaling and the bias are fp32 exactly as in the fp16 kernel (log2 domain, v_exp_f32).  Structure,
 // key-tile geometry, LDS-DMA staging with source-side swizzles and the transposing V reads are those of k_flash_f16 — see
 // the comments there; this file only notes what differs (one K / V tile buffer instead of two: see FlashX3Geom).
+#include "dyn_lds.h"
 #include "ops.h"
 
 namespace sampt {
@@ -363,13 +364,9 @@ int vit_flash_attention_x3(const half_t* qkv, const float* relh, const float* re
 #define FLX(HDv, NWv, SGv)                                                                                              \
   do {                                                                                                                  \
     typedef FlashX3Geom<HDv, NWv, SGv> G;                                                                               \
-    static bool raised = false;                                                                                         \
+    static DeviceOnce once;                                                                                             \
     auto kern = k_flash_x3<HDv, NWv, SGv>;                                                                              \
-    if (!raised) {                                                                                                      \
-      if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS) != hipSuccess)     \
-        return SAMPT_ERR_HIP;                                                                                           \
-      raised = true;                                                                                                    \
-    }                                                                                                                   \
+    SAMPT_TRY(allow_dynamic_lds(once, (const void*)kern, G::LDS, "vit_flash_attention_x3"));                            \
     hipLaunchKernelGGL(kern, dim3(cdiv(N, NWv * 32) * heads * B), dim3(NWv * 64), G::LDS, s, qkv, relh, relw, out, N,   \
                        heads, scale, pad, B, SGv < 64 ? heads : 0);   /* work order: as attention.hip */                \
   } while (0)

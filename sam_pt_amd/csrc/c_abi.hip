@@ -19,6 +19,8 @@ static int fail(int rc, const std::string& msg) {
   g_err = msg;
   return rc;
 }
+// a caller's workspace for the fused InstanceNorm statistics (doubles, written by the convolution kernels)
+static bool stats_ws_bad(const void* ws) { return !ws || ((uintptr_t)ws & 7); }
 static WeightMap make_map(const char* const* names, const void* const* ptrs, int n) {
   WeightMap w;
   for (int i = 0; i < n; ++i) w.m[names[i]] = ptrs[i];
@@ -346,8 +348,6 @@ int sampt_pips_set_mixer(int fused, int workgroups) {
   if (fused < 0 || fused > 2 || workgroups < 1 || workgroups > 1024)
     return fail(SAMPT_ERR_ARG, "sampt_pips_set_mixer: fused 0 / 1 / 2, workgroups 1 .. 1024");
   sampt::g_pips_mixer_fused = fused ? 1 : 0, sampt::g_pips_mixer_x3 = fused == 2, sampt::g_pips_mixer_wgs = workgroups;
-  const char* d = getenv("SAMPT_PIPS_MIXER_DIAG");      // measurement builds only: see pips_mixer.hip g_pips_mixer_diag
-  sampt::g_pips_mixer_diag = d ? atoi(d) : 0;
   return SAMPT_OK;
 }
 
@@ -1518,15 +1518,21 @@ int sampt_gemm_x3_rows(const float* A, const void* w_hl, const float* bias, cons
 int sampt_gemm_x3_rows_epi(const float* A, const void* w_hl, const float* bias, const float* res, int res_mod, float* C, int M, int N,
                            int K, int act, int shuf_g, int epi, const float* epi_a, const float* epi_b, float epi_eps, int epi_ld,
                            sampt_stream_t stream) {
-  GemmP p = gemm_linear(A, K, nullptr, bias, C, epi == 2 ? 1 : (shuf_g ? N / 4 : N), M, N, K, act, res, shuf_g ? N / 4 : N, res_mod);
+  GemmP p = gemm_linear(A, K, nullptr, bias, C, shuf_g ? N / 4 : N, M, N, K, act, res, shuf_g ? N / 4 : N, res_mod);
   gemm_split_planes(p, (const half_t*)w_hl);
   p.shuf_g = shuf_g, p.shuf_n = shuf_g ? N / 4 : 0;
+  if (!epi) return conv_f16x3(p, (hipStream_t)stream);
+  // the fused tails exist in the weights-resident kernel only: refuse rather than compute something else.  The operands are checked
+  // as those of the plain launch, then the tail's own: both kernels read epi_a / epi_b one float at a time
+  const int rc = x3_args_check(p);
+  const bool tail_b = epi == 1 || epi == 3;
+  if (rc == SAMPT_ERR_ARG || !epi_a || (tail_b && !epi_b) || (((uintptr_t)epi_a | (uintptr_t)epi_b) & 3))
+    return fail(SAMPT_ERR_ARG, "sampt_gemm_x3_rows_epi: A, w_hl, C (and bias, res) non-null and 16-byte aligned, epi_a / epi_b non-null floats");
   p.epi = epi, p.epi_a = epi_a, p.epi_b = epi_b, p.epi_eps = epi_eps, p.epi_ld = epi_ld;
-  if (epi) {       // the fused tails exist in the weights-resident kernel only: refuse rather than compute something else
-    if (!sampt::g_gemm_x3_wres || !(epi == 3 ? gemm_x3_wres_ln_eligible(p) : gemm_x3_wres_eligible(p))) return fail(SAMPT_ERR_UNSUPPORTED, "sampt_gemm_x3_rows_epi: shape without a fused tail");
-    return gemm_x3_wres(p, (hipStream_t)stream);
-  }
-  return conv_f16x3(p, (hipStream_t)stream);
+  if (epi == 2) p.ldc = 1;      // one float per output pixel
+  if (rc != SAMPT_OK || !sampt::g_gemm_x3_wres || !(epi == 3 ? gemm_x3_wres_ln_eligible(p) : gemm_x3_wres_eligible(p)))
+    return fail(SAMPT_ERR_UNSUPPORTED, "sampt_gemm_x3_rows_epi: shape without a fused tail");
+  return gemm_x3_wres(p, (hipStream_t)stream);
 }
 
 int sampt_sam_mask_dot(const float* up, const float* hyper, int ld_hyper, float* low, int frames, int npix, int C, sampt_stream_t stream) {
@@ -1542,8 +1548,9 @@ int sampt_fill_f32(float* dst, size_t n, float value, sampt_stream_t stream) { r
 
 int sampt_conv_stem7x7(const float* x_nhwc4, const float* w, const float* bias, float* y, int n, int H, int W, float eps,
                        float* mean_rstd, void* ws, size_t ws_bytes, sampt_stream_t stream) {
+  if (mean_rstd && stats_ws_bad(ws)) return fail(SAMPT_ERR_ARG, "sampt_conv_stem7x7: ws holds doubles: non-null, 8-byte aligned");
   const int chunks = conv_stem_tiles(H, W);
-  if (mean_rstd && ws_bytes < (size_t)n * chunks * 64 * 2 * sizeof(double)) return SAMPT_ERR_WORKSPACE;
+  if (mean_rstd && ws_bytes <(size_t)n * chunks * 64 * 2 * sizeof(double)) return SAMPT_ERR_WORKSPACE;
   SAMPT_TRY(conv_stem7x7_x3(x_nhwc4, w, bias, y, n, H, W, mean_rstd ? (double*)ws : nullptr, (hipStream_t)stream));
   if (!mean_rstd) return SAMPT_OK;
   const long hw = (long)((H + 6 - 7) / 2 + 1) * ((W + 6 - 7) / 2 + 1);
@@ -1556,7 +1563,11 @@ int sampt_conv3x3_planes_instnorm_stats(const void* x_hl, const void* w_hl, cons
   GemmP p = gemm_conv(c, x_hl, n, H, W, y);
   gemm_split_planes(p, c.w_hl);
   p.A_lo = (const half_t*)x_hl + (size_t)n * H * W * Cin;
-  if (!conv3x3_halo_eligible(p)) return fail(SAMPT_ERR_UNSUPPORTED, "sampt_conv3x3_planes_instnorm_stats: Cin % 32, Cout % 4");
+  const int rc = x3_args_check(p);
+  if (rc == SAMPT_ERR_ARG || !mean_rstd || stats_ws_bad(ws))
+    return fail(SAMPT_ERR_ARG, "sampt_conv3x3_planes_instnorm_stats: x_hl, w_hl, y (and bias) non-null and 16-byte aligned, mean_rstd non-null, "
+                               "ws non-null and 8-byte aligned");
+  if (rc != SAMPT_OK || !conv3x3_halo_eligible(p)) return fail(SAMPT_ERR_UNSUPPORTED, "sampt_conv3x3_planes_instnorm_stats: Cin % 32, Cout % 4");
   const int chunks = conv3x3_halo_tiles(p);
   if (ws_bytes < (size_t)n * chunks * Cout * 2 * sizeof(double)) return SAMPT_ERR_WORKSPACE;
   p.in_part = (double*)ws;

@@ -237,9 +237,9 @@ __device__ __forceinline__ long hm_col_term(const GemmP& p, int col) {
 }
 
 extern int g_p8_sched;     // gemm_f16_p8.hip: 0 = stage in the read segments (default), 1 = the round-3 schedule (sampt_gemm_set_schedule)
-extern int g_p8_stagger;
+extern int g_p8_stagger;   // gemm_f16_p8.hip: process-wide default of GemmP::p8_stagger (sampt_gemm_set_stagger)
 extern int g_p8_trim;
-extern int g_thin_min_wgs; // gemm.hip: workgroups a thin f32 GEMM must keep when it grows its tile (sampt_gemm_set_thin_min_wgs)   // gemm_f16_p8.hip: process-wide default of GemmP::p8_stagger (sampt_gemm_set_stagger)
+extern int g_thin_min_wgs; // gemm.hip: workgroups a thin f32 GEMM must keep when it grows its tile (sampt_gemm_set_thin_min_wgs)
 int gemm_f32(const GemmP& p, hipStream_t s);
 int gemm_f16(const GemmP& p, hipStream_t s);
 // the split-K factor gemm_f32 will choose for this problem (1 = no split; needs p.splitk_ws / splitk_ws_floats set)
@@ -259,6 +259,10 @@ extern int g_halo_dbg;
 extern int g_conv_in_stats;    // conv_halo_x3.hip: 1 (default) = the tracker encoder's halo convolutions also sum the following InstanceNorm's
                                // statistics (sampt_conv_set_halo(3) turns it off for A / B runs)
 bool conv3x3_halo_eligible(const GemmP& p);
+// conv_f16x3.hip: what conv_f16x3 asks of every launch of the family before it dispatches — non-null, 16-byte aligned operands
+// (float4 / LDS-DMA loads) and the shapes the kernels take; SAMPT_OK, SAMPT_ERR_ARG or SAMPT_ERR_UNSUPPORTED.  Entry points that
+// call conv3x3_halo_x3 / gemm_x3_wres directly call it first
+int x3_args_check(const GemmP& p);
 // gemm_x3_wres.hip: the tall short-K 1 x 1 case over f32 activations (the mask decoder's image-side projections) with the weight
 // slice resident in LDS; conv_f16x3 hands eligible launches over unless g_gemm_x3_wres == 0
 extern int g_gemm_x3_wres;

@@ -18,6 +18,7 @@
 // barrier per slab; MFMAs are issued with swapped operands so each lane owns 4 consecutive output channels (16-byte
 // stores).
 #include "common.h"
+#include "dyn_lds.h"
 
 namespace sampt {
 
@@ -352,8 +353,7 @@ __global__ __launch_bounds__(256, BN >= 128 ? 3 : 4) void k_conv_f16x3_dma(GemmP
   }
 }
 
-int conv_f16x3(const GemmP& p_in, hipStream_t s) {
-  GemmP p = p_in;
+int x3_args_check(const GemmP& p) {
   if (!p.A || !p.W || !p.W_lo || !p.C || p.M <= 0 || p.N <= 0) return SAMPT_ERR_ARG;
   if (!p.conv || p.cC % 32 || p.K != p.KH * p.KW * p.cC || p.ldw % 8 || p.N % 4 || p.ldc % 4) return SAMPT_ERR_UNSUPPORTED;
   if (p.shuf_g && (p.shuf_n <= 0 || p.shuf_n % 4 || p.N != 4 * p.shuf_n || p.M % (p.shuf_g * p.shuf_g))) return SAMPT_ERR_ARG;
@@ -361,6 +361,11 @@ int conv_f16x3(const GemmP& p_in, hipStream_t s) {
   if (((uintptr_t)p.A | (uintptr_t)p.A_lo | (uintptr_t)p.W | (uintptr_t)p.W_lo | (uintptr_t)p.C | (uintptr_t)p.bias |
        (uintptr_t)p.res) & 15)
     return SAMPT_ERR_ARG;
+  return SAMPT_OK;
+}
+
+int conv_f16x3(const GemmP& p, hipStream_t s) {
+  SAMPT_TRY(x3_args_check(p));
   // (Round 6 tried a kernel of its own for the tall, short-K 1 x 1 case — the mask decoder's image-side projections, M = 98 304,
   //  K = 256, N = 256 .. 512: 128 rows x all N per workgroup, A straight into operand registers, W through a 4-slot LDS-DMA ring —
   //  and measured 99.7 / 132.6 / 169.6 us against 98.6 / 152.2 / 190.1 us here, 208.1 vs 209.0 ms per clip: both sit at ~2 TB/s of
@@ -385,14 +390,11 @@ int conv_f16x3(const GemmP& p_in, hipStream_t s) {
   // One K slab of register prefetch.  Two slabs in flight (a second register set) measured slower everywhere — decode chain
   // 24.70 vs 24.34 ms, tracker-encoder pass 6.54 vs 6.08 ms (profiles/r2_v16_*): these kernels are not bound by the latency of
   // their global loads, and the extra 30 registers cost the 64- and 96-column tiles a resident wave.
-  static bool raised = false;
-  if (!raised) {  // 128 x 128 tiles need 80 KiB, above the default 64 KiB dynamic-LDS limit (gfx950: 160 KiB per CU)
-    const void* fns[] = {(const void*)k_conv_f16x3<128, 64, 1>, (const void*)k_conv_f16x3<128, 96, 1>,
-                         (const void*)k_conv_f16x3<128, 128, 1>};
-    for (const void* f : fns)
-      if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess) return SAMPT_ERR_HIP;
-    raised = true;
-  }
+  // 128 x 128 tiles need 80 KiB, above the default 64 KiB dynamic-LDS limit (gfx950: 160 KiB per CU)
+  const void* fns[3] = {(const void*)k_conv_f16x3<128, 64, 1>, (const void*)k_conv_f16x3<128, 96, 1>,
+                        (const void*)k_conv_f16x3<128, 128, 1>};
+  static DeviceOnce once[3];
+  for (int i = 0; i < 3; ++i) SAMPT_TRY(allow_dynamic_lds(once[i], fns[i], 80 * 1024, "conv_f16x3"));
   dim3 grid((unsigned)((long)cdiv(p.N, BN) * cdiv(p.M, 128))), block(256);
 #define CONV_LAUNCH(BNv) hipLaunchKernelGGL((k_conv_f16x3<128, BNv, 1>), grid, block, lds, s, p)
   if (BN == 32) CONV_LAUNCH(32);   // (51 KiB: under the default limit)

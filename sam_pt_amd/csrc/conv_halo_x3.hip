@@ -16,6 +16,7 @@
 // F = {0, 3, 2, 1}; fragment reads apply the same XOR), taps outside the image read a page of zeros.
 #include <type_traits>
 
+#include "dyn_lds.h"
 #include "ops.h"
 
 namespace sampt {
@@ -288,13 +289,9 @@ int conv3x3_halo_x3(const GemmP& p, hipStream_t s) {
   do {                                                                                                                   \
     constexpr bool A2v = A2x;                                                                                            \
     constexpr int LDSB = (A2v ? 2 : 1) * ABUF + 1024 + 4 * (BNv * 64 * 2);                                               \
-    static bool raised = false;                                                                                          \
+    static DeviceOnce once;                                                                                              \
     auto kern = k_conv3x3_halo_x3<BNv, A2v, NWVv>;                                                                       \
-    if (!raised) {                                                                                                       \
-      if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024 > LDSB ? 100 * 1024 : LDSB) != hipSuccess)        \
-        return SAMPT_ERR_HIP;                                                                                            \
-      raised = true;                                                                                                     \
-    }                                                                                                                    \
+    SAMPT_TRY(allow_dynamic_lds(once, (const void*)kern, 100 * 1024 > LDSB ? 100 * 1024 : LDSB, "conv3x3_halo_x3"));     \
     hipLaunchKernelGGL(kern, grid, dim3(NWVv * 64), (g_halo_dbg == 7 && LDSB < 100 * 1024) ? 100 * 1024 : LDSB, s, p, ntx, nty, g_halo_dbg == 8 ? 0 : 1);  \
   } while (0)
   const bool w8 = g_conv_halo != 2;

@@ -11,6 +11,7 @@
 //     into MFMA operand images in LDS; workgroups are persistent (two per CU) so that this happens 512 times, not 4608;
 //   * a wave owns 4 rows of the tile x all 64 channels: per kernel row 8 + 8 ds_read_b128 against 48 MFMAs;
 //   * same epilogue as conv_halo_x3.hip: alpha, bias, 16-byte stores, per-tile InstanceNorm partial sums (GemmP::in_part layout).
+#include "dyn_lds.h"
 #include "ops.h"
 
 namespace sampt {
@@ -167,11 +168,8 @@ int conv_stem7x7_x3(const float* x, const float* w, const float* bias, float* y,
   const int OH = (H + 6 - 7) / 2 + 1, OW = (W + 6 - 7) / 2 + 1;
   const int ntx = cdiv(OW, ST), nty = cdiv(OH, ST);
   const int ldsb = WIMG + 2 * ((PLANE + 15) & ~15);
-  static bool raised = false;
-  if (!raised) {
-    if (hipFuncSetAttribute((const void*)k_stem7x7s2_x3, hipFuncAttributeMaxDynamicSharedMemorySize, ldsb) != hipSuccess) return SAMPT_ERR_HIP;
-    raised = true;
-  }
+  static DeviceOnce once;
+  SAMPT_TRY(allow_dynamic_lds(once, (const void*)k_stem7x7s2_x3, ldsb, "conv_stem7x7_x3"));
   const long ntiles = (long)nimg * ntx * nty;
   const int grid = (int)(ntiles < 512 ? ntiles : 512);
   hipLaunchKernelGGL(k_stem7x7s2_x3, dim3(grid), dim3(256), ldsb, s, (const float4*)x, w, bias, y, in_part, nimg, H, W, OH, OW, ntx, nty);

@@ -8,8 +8,7 @@
 // the softmax-weighted mean over the radius-5 disk, the occlusion branch, the query-frame override.  Geometry: 256 x 256 frames, a
 // 32 x 32 x 256 channel-normalised grid per frame (NHWC f32).
 #pragma once
-#include <string>
-
+#include "dyn_lds.h"
 #include "ops.h"
 
 namespace sampt {
@@ -184,14 +183,10 @@ int cost_volume_heads(const char* who, const float* lowres, int T, const float* 
     return SAMPT_ERR_ARG;
   if ((long)n * T > 0x7fffffffL) return SAMPT_ERR_ARG;
   if (!w.w1 || !w.b1 || !w.w2 || !w.b2 || !w.w3 || !w.b3 || !w.w4 || !w.b4 || !w.w5 || !w.b5) return SAMPT_ERR_ARG;
-  // 74 KiB of dynamic LDS, above the default 64 KiB limit (gfx950: 160 KiB per CU).  The attribute belongs to the current device, so it is
-  // set on every call (a host-side store, no device work) and not remembered per process.
+  // 74 KiB of dynamic LDS, above the default 64 KiB limit (gfx950: 160 KiB per CU)
   auto kern = k_cost_volume_heads<TEMP, NOUT, OCC_RELU>;
-  const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HD_LDS_BYTES);
-  if (e != hipSuccess) {
-    set_error((std::string(who) + ": hipFuncSetAttribute").c_str(), e);
-    return SAMPT_ERR_HIP;
-  }
+  static DeviceOnce once;
+  SAMPT_TRY(allow_dynamic_lds(once, (const void*)kern, (int)HD_LDS_BYTES, who));
   hipLaunchKernelGGL(kern, dim3((unsigned)((long)n * T)), dim3(256), HD_LDS_BYTES, s, lowres, T, qf, ldq, qoff, q, w, pts, occ, expd, iter_out);
   SAMPT_CHECK_LAUNCH(who);
   return SAMPT_OK;

@@ -25,6 +25,7 @@
 //     activation, residual), so the results are BITWISE those of the kernel it replaces (tests/test_gpu_kernels.py).
 #include <type_traits>
 
+#include "dyn_lds.h"
 #include "ops.h"
 
 namespace sampt {
@@ -481,11 +482,8 @@ bool gemm_x3_wres_ln_eligible(const GemmP& p) {
 
 int gemm_x3_wres_ln(const GemmP& p, hipStream_t s) {
   constexpr int LDSB = 4 * 16 * 2 * 1024 + 3 * 1024;
-  static bool raised = false;
-  if (!raised) {
-    if (hipFuncSetAttribute((const void*)k_gemm_x3_wres_ln, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB) != hipSuccess) return SAMPT_ERR_HIP;
-    raised = true;
-  }
+  static DeviceOnce once;
+  SAMPT_TRY(allow_dynamic_lds(once, (const void*)k_gemm_x3_wres_ln, LDSB, "gemm_x3_wres_ln"));
   hipLaunchKernelGGL(k_gemm_x3_wres_ln, dim3(256), dim3(512), LDSB, s, p);
   SAMPT_CHECK_LAUNCH("gemm_x3_wres_ln");
   return SAMPT_OK;
@@ -499,14 +497,10 @@ int gemm_x3_wres(const GemmP& p, hipStream_t s) {
   const int ldsb = KS * 16 * 1024 + 512 + epib;
 #define WRES(KSv, RESv, ACTv, EPIv)                                                                                      \
   do {                                                                                                                   \
-    static bool raised = false;                                                                                          \
+    static DeviceOnce once;                                                                                              \
     auto kern = k_gemm_x3_wres<KSv, RESv, ACTv, EPIv>;                                                                   \
-    if (!raised) {                                                                                                       \
-      if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,                             \
-                              KSv * 16 * 1024 + 512 + (EPIv == 2 ? 128 * 128 : 512)) != hipSuccess)                      \
-        return SAMPT_ERR_HIP;                                                                                            \
-      raised = true;                                                                                                     \
-    }                                                                                                                    \
+    SAMPT_TRY(allow_dynamic_lds(once, (const void*)kern, KSv * 16 * 1024 + 512 + (EPIv == 2 ? 128 * 128 : 512),          \
+                                "gemm_x3_wres"));                                                                        \
     hipLaunchKernelGGL(kern, dim3(256), dim3(512), ldsb, s, p, S, RL);                                                   \
   } while (0)
   if (p.epi == 1) WRES(8, false, ACT_GELU, 1);

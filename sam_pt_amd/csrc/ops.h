@@ -165,7 +165,7 @@ int pips_round_begin(const int* cur, const unsigned char* flip, const float* tra
 int pips_round_end(int* cur, const float* tr, const float* vi, int T, int n, int S, float thr0, float* traj, float* vis,
                    int* n_active, hipStream_t s);
 // ---- pips_mixer.hip: the mixer's channel MLP + everything between two channel MLPs, two launches per block (file header)
-extern int g_pips_mixer_fused, g_pips_mixer_wgs, g_pips_mixer_diag;
+extern int g_pips_mixer_fused, g_pips_mixer_wgs;
 // hidden slices (8, 16 or 32) a channel-MLP launch over nseq sequences uses to reach g_pips_mixer_wgs workgroups
 int pips_mix_slices(int nseq);
 // part[slice][nseq*8][512] = fc2 over the slice's hidden units of gelu(fc1(LN(x)) + b1); x [nseq*8][512]

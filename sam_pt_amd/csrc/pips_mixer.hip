@@ -39,7 +39,7 @@ __device__ __forceinline__ float4 ld4(const float* p) { return *(const float4*)p
 // wants (declared, so that keeping 8 chunks of weights in flight is not "register pressure" to the scheduler).
 #define MIX_PIN() __builtin_amdgcn_sched_barrier(0)
 
-template <int NF, int DIAG>
+template <int NF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_pips_mix_mlp(const float* __restrict__ x, const float* __restrict__ lnw,
                                                       const float* __restrict__ lnb, const float* __restrict__ w1,
                                                       const float* __restrict__ b1, const float* __restrict__ w2,
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     float4 wv[NF][2];
 #pragma unroll
     for (int f = 0; f < NF; ++f) wv[f][0] = wq[c2 % PD][f][0], wv[f][1] = wq[c2 % PD][f][1];
-    if (c2 + PD < 16 && !DIAG) {
+    if (c2 + PD < 16) {
 #pragma unroll
       for (int f = 0; f < NF; ++f) {
         wq[c2 % PD][f][0] = ld4(w1p + (long)f * 16 * MD + (c2 + PD) * 32);
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   float* prow = part + ((long)slice * R + r0 + lr) * MD + lq * 4;
 #pragma unroll
   for (int g = 0; g < NG; ++g) {
-    if (g + 2 < NG && !DIAG) load_w2(g + 2, (g + 2) % 3);
+    if (g + 2 < NG) load_w2(g + 2, (g + 2) % 3);
     MIX_PIN();
     f32x4 acc2[OG];
 #pragma unroll
@@ -322,8 +322,6 @@ int g_pips_mixer_fused = 1;     // sampt_pips_set_mixer: 1 = the two-launch bloc
 // split-fp16 kernel 16 (< 32) or 32 slices per 64 rows.  Default 16: beside the encoder's 30 persistent GEMM workgroups per XCD
 // the chain then needs exactly the two CUs per XCD they leave (profiles/r6_c5_*, r6_c7_*: 113.9 fps against 111.8 with 32 / 28).
 int g_pips_mixer_wgs = 16;
-int g_pips_mixer_diag = 0;      // measurement only (SAMPT_PIPS_MIXER_DIAG=1): steady-state weight loads skipped — WRONG results, the
-                                // launch's time without its weight stream
 
 int pips_mix_slices(int nseq) {
   const int rgs = (nseq + 1) / 2;
@@ -337,12 +335,8 @@ int pips_mix_mlp(const float* x, const float* lnw, const float* lnb, const float
   if (nseq <= 0 || (NS != 8 && NS != 16 && NS != 32)) return SAMPT_ERR_ARG;
   const int R = nseq * 8, rgs = (nseq + 1) / 2;
   dim3 grid(rgs * NS), block(256);
-#define MIXM(NFv, DIAGv) hipLaunchKernelGGL((k_pips_mix_mlp<NFv, DIAGv>), grid, block, 0, s, x, lnw, lnb, w1, b1, w2, part, R, NS)
-  if (g_pips_mixer_diag) {
-    if (NS == 8) MIXM(4, 1); else if (NS == 16) MIXM(2, 1); else MIXM(1, 1);
-  } else {
-    if (NS == 8) MIXM(4, 0); else if (NS == 16) MIXM(2, 0); else MIXM(1, 0);
-  }
+#define MIXM(NFv) hipLaunchKernelGGL(k_pips_mix_mlp<NFv>, grid, block, 0, s, x, lnw, lnb, w1, b1, w2, part, R, NS)
+  if (NS == 8) MIXM(4); else if (NS == 16) MIXM(2); else MIXM(1);
 #undef MIXM
   SAMPT_CHECK_LAUNCH("pips_mix_mlp");
   return SAMPT_OK;

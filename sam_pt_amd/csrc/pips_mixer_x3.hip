@@ -16,6 +16,7 @@
 //     the operand images of the input directly; this kernel's prologue is 32 coalesced 16-byte loads per lane.
 #include <type_traits>
 
+#include "dyn_lds.h"
 #include "ops.h"
 
 namespace sampt {
@@ -314,13 +315,9 @@ int pips_mix_mlp_x3(const half_t* xop, const half_t* wstream, const float* b1, f
   dim3 grid(rts * NS), block(256);
 #define MIXX(NFv)                                                                                                        \
   do {                                                                                                                   \
-    static bool raised = false;                                                                                          \
+    static DeviceOnce once;                                                                                              \
     auto kern = k_pips_mix_mlp_x3<NFv>;                                                                                  \
-    if (!raised) {                                                                                                       \
-      if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB) != hipSuccess)        \
-        return SAMPT_ERR_HIP;                                                                                            \
-      raised = true;                                                                                                     \
-    }                                                                                                                    \
+    SAMPT_TRY(allow_dynamic_lds(once, (const void*)kern, LDSB, "pips_mix_mlp_x3"));                                      \
     hipLaunchKernelGGL(kern, grid, block, LDSB, s, xop, wstream, b1, part, R, NS);                                       \
   } while (0)
   if (NS == 16) MIXX(8); else MIXX(4);

@@ -2,6 +2,7 @@
 // Every kernel carries a frame-batch dimension F: the per-(frame, object) prompt chains of one clip are independent,
 // so the engine runs pass r of ALL frames as one launch (tokens [F][Nt][256], image tokens [F][4096][256]) instead of
 // F latency-bound single-frame launches.
+#include "dyn_lds.h"
 #include "ops.h"
 #include "sam_postprocess.h"
 
@@ -680,15 +681,9 @@ int attn_fewkeys(const float* q, const float* k, const float* v, float* out, int
   const bool stage = heads * hd == 128;
   size_t sh = ((size_t)2 * chunk * heads * hd + (stage ? 32 * 132 : 0)) * sizeof(float);
   if (sh > 64 * 1024) {  // above the default dynamic-LDS limit (gfx950 has 160 KiB per workgroup)
-    static bool raised = false;
-    if (!raised) {
-      if (hipFuncSetAttribute((const void*)k_attn_fewkeys<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              152 * 1024) != hipSuccess ||
-          hipFuncSetAttribute((const void*)k_attn_fewkeys<16, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              144 * 1024) != hipSuccess)
-        return SAMPT_ERR_HIP;
-      raised = true;
-    }
+    static DeviceOnce staged, plain;
+    SAMPT_TRY(allow_dynamic_lds(staged, (const void*)k_attn_fewkeys<16, true>, 152 * 1024, "attn_fewkeys"));
+    SAMPT_TRY(allow_dynamic_lds(plain, (const void*)k_attn_fewkeys<16, false>, 144 * 1024, "attn_fewkeys"));
   }
   if (stage)
     hipLaunchKernelGGL((k_attn_fewkeys<16, true>), dim3(cdiv((long)Nq * heads, 256), F), dim3(256), sh, s, q, k, v, out, Nq,

@@ -725,6 +725,78 @@ def test_c_abi_error_behaviour_without_a_gpu():
         _lib.check(-1, "context")
 
 
+def test_x3_entry_points_refuse_bad_pointers_without_a_gpu():
+    """sampt_gemm_x3_rows_epi (epi != 0) and sampt_conv3x3_planes_instnorm_stats dispatch to gemm_x3_wres / conv3x3_halo_x3
+    themselves, so they make conv_f16x3's operand checks (x3_args_check) and their own before anything is launched: a NULL or
+    misaligned pointer is SAMPT_ERR_ARG with a message, an unsupported shape stays SAMPT_ERR_UNSUPPORTED, a short workspace
+    SAMPT_ERR_WORKSPACE.  Nothing is dereferenced before the checks, so made-up addresses stand in for device pointers."""
+    from sam_pt_amd import _lib
+    lib = _lib.load()
+    ARG, UNSUPPORTED, WORKSPACE = -1, -3, -4
+    base = 0x7F0000000000                      # 16-byte aligned "buffers", 1 MiB apart
+    A, WHL, BIAS, RES, C_, EA, EB, MR, WS = (base + (i << 20) for i in range(9))
+
+    def refused(call, good, slot, bad):
+        args = list(good)
+        args[slot] = bad
+        lib.sampt_pips_set_mixer(9, 0)         # (leaves a known message behind: the next one must replace it)
+        assert "sampt_pips_set_mixer" in lib.sampt_last_error().decode()
+        rc = call(*args)
+        msg = lib.sampt_last_error().decode()
+        return rc, (msg if "sampt_pips_set_mixer" not in msg else "")
+
+    # A, w_hl, bias, res, res_mod, C, M, N, K, act, shuf_g, epi, epi_a, epi_b, eps, epi_ld, stream: the shapes of
+    # test_gemm_x3_rows_fused_upscaling_tails (epi = 1) and test_gemm_x3_rows_fused_layernorm_tail (epi = 3)
+    tails = {1: [A, WHL, BIAS, None, 0, C_, 4 * 4096, 256, 256, 2, 64, 1, EA, EB, 1e-6, 0, None],
+             3: [A, WHL, BIAS, C_, 0, C_, 5 * 4096 + 5, 256, 128, 0, 0, 3, EA, EB, 1e-5, 0, None]}
+    for epi, good in tails.items():
+        # A, w_hl and C are read / written 16 bytes at a time: + 4 is misaligned.  The tail vectors are read one float at a time
+        # (k_gemm_x3_wres, k_gemm_x3_wres_ln), so a 4-byte aligned epi_a is legal: its bad address has bits 1 and 2 set
+        for slot, off in ((0, 4), (1, 4), (5, 4), (12, 6)):
+            for bad in (None, good[slot] + off):
+                rc, msg = refused(lib.sampt_gemm_x3_rows_epi, good, slot, bad)
+                assert rc == ARG and "sampt_gemm_x3_rows_epi" in msg, (epi, slot, bad, rc, msg)
+        rc, msg = refused(lib.sampt_gemm_x3_rows_epi, good, 13, None)             # both tails read epi_b too
+        assert rc == ARG and msg
+        rc, msg = refused(lib.sampt_gemm_x3_rows_epi, good, 7, 128 if epi == 1 else 512)      # N the tail does not take
+        assert rc == UNSUPPORTED and "fused tail" in msg, (epi, rc, msg)
+
+    # x_hl, w_hl, bias, y, n, H, W, Cin, Cout, eps, mean_rstd, ws, ws_bytes, stream: test_conv3x3_fused_instnorm_statistics' first shape
+    n, H, W, Cin, Cout = 2, 32, 48, 64, 64
+    need = n * ((H + 15) // 16) * ((W + 15) // 16) * Cout * 2 * 8
+    good = [A, WHL, BIAS, C_, n, H, W, Cin, Cout, 1e-5, MR, WS, need, None]
+    for slot in (0, 1, 3, 11):
+        for bad in (None, good[slot] + 4):                                         # (ws holds doubles: + 4 is misaligned for it too)
+            rc, msg = refused(lib.sampt_conv3x3_planes_instnorm_stats, good, slot, bad)
+            assert rc == ARG and "sampt_conv3x3_planes_instnorm_stats" in msg, (slot, bad, rc, msg)
+    rc, msg = refused(lib.sampt_conv3x3_planes_instnorm_stats, good, 10, None)
+    assert rc == ARG and msg
+    assert refused(lib.sampt_conv3x3_planes_instnorm_stats, good, 12, need - 1)[0] == WORKSPACE
+    assert refused(lib.sampt_conv3x3_planes_instnorm_stats, good, 7, 48)[0] == UNSUPPORTED      # Cin % 32
+    # the stem's statistics workspace, same rule (x, w, bias, y, n, H, W, eps, mean_rstd, ws, ws_bytes, stream)
+    stem = [A, WHL, BIAS, C_, 1, 32, 32, 1e-5, MR, WS, 1 << 20, None]
+    for bad in (None, WS + 4):
+        rc, msg = refused(lib.sampt_conv_stem7x7, stem, 9, bad)
+        assert rc == ARG and "sampt_conv_stem7x7" in msg
+    assert refused(lib.sampt_conv_stem7x7, stem, 10, 8)[0] == WORKSPACE
+
+
+def test_device_once_host_program_under_thread_sanitizer(tmp_path):
+    """DeviceOnce (csrc/dyn_lds.h: which devices a kernel's dynamic-LDS limit has been raised on) alone, as a host program of its
+    own (tests/device_once_main.cpp) built with the host compiler and -fsanitize=thread: 8 threads over 4 ordinals, the callable
+    succeeds once per ordinal, a failed first call is tried again, an ordinal outside the table runs it every time."""
+    import shutil
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path / "device_once")
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-pthread", "-fsanitize=thread", os.path.join(ROOT, "tests", "device_once_main.cpp"), "-o", exe]
+    built = subprocess.run(cmd, capture_output=True, text=True)
+    assert built.returncode == 0, built.stderr
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0 and "device_once: ok" in run.stdout, run.stdout + run.stderr
+    assert "ThreadSanitizer" not in run.stderr
+
+
 def test_split_f16x3_weights_and_per_tracker_default(monkeypatch):
     """Host side of csrc/conv_f16x3.hip: hi + lo reproduces w * 2^8 to fp32 precision (absolute error far below one fp32
     ulp of the layer's largest weight), out-of-range weights are refused, and the split planes are packed for PIPS by

@@ -1069,26 +1069,32 @@ def test_pips_mix_pre(lib, dev, nseq, slices):
     assert (got - y2).abs().max().item() < 4e-6 * max(1.0, y2.abs().max().item())
 
 
-@pytest.mark.parametrize("nseq,slices", [(8, 16), (8, 32), (3, 16), (1, 32), (24, 16), (9, 32)])
-def test_pips_mix_mlp_x3_slabs(lib, dev, nseq, slices):
-    """fc1 -> GELU -> fc2 over hidden slices as 3-term split-fp16 products from the packed weight stream: every slab against
-    the fp64 product of its own slice, at fp32 grade."""
+def _mix_mlp_x3_operands(nseq, slices):
+    """Host side of a sampt_pips_mix_mlp_x3 launch: the block's weights, LayerNorm(x) in fp64, the operand images of the input built
+    the way k_pips_mix_pre writes them, the packed weight stream."""
     from sam_pt_amd.pack import pips_mixer_x3_stream
     x, w = _mixer_block_inputs(nseq, 400 + nseq + slices)
     R = nseq * 8
     y = F.layer_norm(x.double(), (512,), w["lnw"].double(), w["lnb"].double(), 1e-5)
-    h = F.gelu(y @ w["w1"].double().t() + w["b1"].double())
-    hs = 2048 // slices
-    ref = torch.stack([h[:, s * hs:(s + 1) * hs] @ w["w2"].double()[:, s * hs:(s + 1) * hs].t() for s in range(slices)])
-    # operand images of the input, built on the host the way k_pips_mix_pre writes them
     nf = (R + 15) // 16
     ys = torch.zeros(nf * 16, 512)
     ys[:R] = (y * 64.0).float()
     hi = ys.half()
     lo = (ys - hi.float()).half()
     img = torch.stack([hi, lo]).view(2, nf, 16, 16, 4, 8).permute(1, 3, 0, 4, 2, 5).contiguous()   # [frag][ks][plane][lq][lr][e]
-    xop = img.reshape(-1).to(dev)
-    ws = pips_mixer_x3_stream(w["w1"], w["w2"], slices).to(dev)
+    return w, y, img.reshape(-1), pips_mixer_x3_stream(w["w1"], w["w2"], slices)
+
+
+@pytest.mark.parametrize("nseq,slices", [(8, 16), (8, 32), (3, 16), (1, 32), (24, 16), (9, 32)])
+def test_pips_mix_mlp_x3_slabs(lib, dev, nseq, slices):
+    """fc1 -> GELU -> fc2 over hidden slices as 3-term split-fp16 products from the packed weight stream: every slab against
+    the fp64 product of its own slice, at fp32 grade."""
+    w, y, xop, ws = _mix_mlp_x3_operands(nseq, slices)
+    R = nseq * 8
+    h = F.gelu(y @ w["w1"].double().t() + w["b1"].double())
+    hs = 2048 // slices
+    ref = torch.stack([h[:, s * hs:(s + 1) * hs] @ w["w2"].double()[:, s * hs:(s + 1) * hs].t() for s in range(slices)])
+    xop, ws = xop.to(dev), ws.to(dev)
     b1 = w["b1"].to(dev)
     part = torch.full((slices, R, 512), float("nan"), device=dev)
     ok(lib.sampt_pips_mix_mlp_x3(P(xop), P(ws), P(b1), P(part), nseq, slices, S()), "mix_mlp_x3")
@@ -1097,6 +1103,35 @@ def test_pips_mix_mlp_x3_slabs(lib, dev, nseq, slices):
     scale = ref.abs().max().item()
     assert (part.cpu().double() - ref).abs().max().item() < 6e-6 * max(scale, 1.0)
     assert rel_err(part.sum(0), ref.sum(0)) < 4e-6
+
+
+def test_dynamic_lds_limit_follows_the_device(lib):
+    """The limit on dynamic LDS belongs to the (kernel, device) pair (csrc/dyn_lds.h): a kernel that needs more than 64 KiB runs on a
+    second device of the same process as on the first — the stem convolution (a plain launch site) and the split-fp16 channel MLP
+    (a macro site), same inputs on cuda:0 then cuda:1, same bits."""
+    from sam_pt_amd import _lib
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two GPUs")
+    g = torch.Generator().manual_seed(32)
+    n, H, W = 1, 32, 32
+    x4 = torch.cat([torch.rand(n, H, W, 3, generator=g) * 2.0 - 1.0, torch.zeros(n, H, W, 1)], 3).contiguous()
+    w4 = torch.cat([torch.randn(64, 7, 7, 3, generator=g) * (2.0 / (64 * 49)) ** 0.5, torch.zeros(64, 7, 7, 1)], 3).contiguous()
+    b = torch.randn(64, generator=g)
+    nseq, slices = 1, 32
+    w, _, xop, ws = _mix_mlp_x3_operands(nseq, slices)
+    outs = []
+    for d in (torch.device("cuda:0"), torch.device("cuda:1")):
+        with _lib.device_guard(d):
+            xd, wd, bd = x4.to(d), w4.to(d), b.to(d)
+            y = torch.full((n, H // 2, W // 2, 64), 7.0, device=d)
+            ok(lib.sampt_conv_stem7x7(P(xd), P(wd), P(bd), P(y), n, H, W, 1e-5, None, None, 0, S()), f"stem on {d}")
+            xopd, wsd, b1d = xop.to(d), ws.to(d), w["b1"].to(d)
+            part = torch.full((slices, nseq * 8, 512), float("nan"), device=d)
+            ok(lib.sampt_pips_mix_mlp_x3(P(xopd), P(wsd), P(b1d), P(part), nseq, slices, S()), f"mix_mlp_x3 on {d}")
+            torch.cuda.synchronize(d)
+            outs.append((y.cpu(), part.cpu()))
+    assert torch.isfinite(outs[0][1]).all() and (outs[0][0] != 7.0).any()
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
 
 
 def test_pips_mixer_x3_equals_f32_paths(lib, dev):
