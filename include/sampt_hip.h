@@ -760,6 +760,32 @@ int sampt_viz_compose(const uint8_t* frames_dev, int interleaved, int n_frames, 
 int sampt_patch_filter(const uint8_t* rgb_dev, int T, int H, int W, const float* query_dev, const float* traj_dev,
                        const float* vis_in_dev, int N, int patch_size, float threshold, const double* companding_dev, int border_rule,
                        float* vis_out_dev, float* sim_out_dev, sampt_stream_t stream);
+/* Prompt assembly of SamPt on the device (csrc/prompt_assembly.hip; the specification is assemble_prompts_host of
+ * sam_pt_amd/prompt_assembly.py, i.e. SamPt._prepare_points followed by ResizeLongestSide.apply_coords, reference sam_pt.py:726-758).
+ * No handle, no scratch memory, no atomics, stream-ordered, bitwise repeatable; inputs are finite.
+ * traj_dev f32 [T][M][P][2]; vis_dev f32 [T][M][P] visibility codes: a point is visible iff its code == 1.0f (0, -1 .. -4 are not).
+ * pp = positive_points_per_mask; negatives != 0 <=> negative_points_per_mask > 0; add_others != 0 <=> other objects' positives are
+ * appended.  Item i = t * M + m.  Its prompt: the object's own visible points in index order — label 1 for index < pp, label 0 for
+ * index >= pp when `negatives`, label 1 throughout otherwise —, then, when M > 1 and `add_others`, the visible points among the first
+ * min(pp, P) of every other object, object-major, label 0.  A coordinate is (float)((double)x * sx) resp. (float)((double)y * sy).
+ * k = prompt length, npos = number of label-1 entries.
+ * sampt_prompt_count: k_all_dev / npos_all_dev int32 [T * M] of every item (the caller downloads them and decides which items run,
+ *   with how many point slots, in which chunks).
+ * sampt_prompt_fill: the n_items items named by items_dev (int32, any subset in any order; a number outside 0 .. T * M - 1 yields an
+ *   empty prompt) -> pts_dev f32 [n_items][ld][2], labels_dev int32 [n_items][ld], both zero from an item's k on; k_item_dev /
+ *   npos_item_dev int32 [n_items].  ld must be at least the largest k of the chunk (entries from slot ld on are dropped, k_item keeps
+ *   the full length).  The outputs are the layout of sampt_sam_track_decode's pts_dev / labels_dev / k_item_dev / npos_item_dev.
+ * sampt_mark_outside_frame: the four border comparisons of SamPt._track_points (sam_pt.py:684-690) over n points: traj_dev f32
+ *   [n][2], vis_out_dev[i] = -2 where x / W < 0.01, y / H < 0.01, x / W > 0.99 or y / H > 0.99 (f32, IEEE division), else
+ *   vis_in_dev[i]; vis_out_dev may be vis_in_dev.
+ * SAMPT_ERR_ARG: a null pointer; T, M, P, n_items, ld, n, H or W <= 0; pp < 0; T * M * P * 2 or n_items * ld * 2 above 2^31 - 1. */
+int sampt_prompt_count(const float* vis_dev, int T, int M, int P, int pp, int negatives, int add_others, int32_t* k_all_dev,
+                       int32_t* npos_all_dev, sampt_stream_t stream);
+int sampt_prompt_fill(const float* traj_dev, const float* vis_dev, int T, int M, int P, int pp, int negatives, int add_others, double sx,
+                      double sy, const int32_t* items_dev, int n_items, int ld, float* pts_dev, int32_t* labels_dev, int32_t* k_item_dev,
+                      int32_t* npos_item_dev, sampt_stream_t stream);
+int sampt_mark_outside_frame(const float* traj_dev, const float* vis_in_dev, long n, int H, int W, float* vis_out_dev,
+                             sampt_stream_t stream);
 /* Whole SamPt.predict_mask chain (sam_pt.py:760-837) for `frames` independent (frame, object) items that share the
  * visible-point count k, batched into one launch sequence and without host synchronisation:
  * [positives-only pass over the first n_pos_first points when n_pos_first >= 0, i.e. negative_points_per_mask > 0;

@@ -204,6 +204,10 @@ _SIGS = {
     "sampt_conv_set_halo": (c_int, [c_int]),
     "sampt_gemm_set_wres": (c_int, [c_int]),
     "sampt_gemm_set_trim": (c_int, [c_int]),
+    "sampt_prompt_count": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "sampt_prompt_fill": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, C.c_double, C.c_double, _P, c_int, c_int, _P, _P, _P,
+                                  _P, _P]),
+    "sampt_mark_outside_frame": (c_int, [_P, _P, C.c_long, c_int, c_int, _P, _P]),
     "sampt_move_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_int, c_int, c_int, c_void_p]),
     "sampt_fill_f32": (c_int, [c_void_p, c_size_t, c_float, c_void_p]),
     "sampt_conv_stem7x7": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_size_t,

@@ -1239,6 +1239,41 @@ int sampt_patch_filter(const uint8_t* rgb, int T, int H, int W, const float* que
                       (hipStream_t)stream);
 }
 
+static int pa_bad_shape(const char* who, int T, int M, int P, int pp) {
+  if (T <= 0 || M <= 0 || P <= 0 || pp < 0 || (long)T * M * P * 2 > 0x7fffffffL)
+    return fail(SAMPT_ERR_ARG, std::string(who) + ": T, M and P must be positive, pp non-negative and T * M * P * 2 below 2^31; got T = " +
+                                   std::to_string(T) + ", M = " + std::to_string(M) + ", P = " + std::to_string(P) + ", pp = " +
+                                   std::to_string(pp));
+  return SAMPT_OK;
+}
+
+int sampt_prompt_count(const float* vis, int T, int M, int P, int pp, int negatives, int add_others, int32_t* k_all, int32_t* npos_all,
+                       sampt_stream_t stream) {
+  if (pa_bad_shape("sampt_prompt_count", T, M, P, pp) != SAMPT_OK) return SAMPT_ERR_ARG;
+  if (!vis || !k_all || !npos_all) return fail(SAMPT_ERR_ARG, "sampt_prompt_count: null pointer");
+  return prompt_count(vis, T, M, P, pp, negatives, add_others, (int*)k_all, (int*)npos_all, (hipStream_t)stream);
+}
+
+int sampt_prompt_fill(const float* traj, const float* vis, int T, int M, int P, int pp, int negatives, int add_others, double sx, double sy,
+                      const int32_t* items, int n_items, int ld, float* pts, int32_t* labels, int32_t* k_item, int32_t* npos_item,
+                      sampt_stream_t stream) {
+  if (pa_bad_shape("sampt_prompt_fill", T, M, P, pp) != SAMPT_OK) return SAMPT_ERR_ARG;
+  if (n_items <= 0 || ld <= 0 || (long)n_items * ld * 2 > 0x7fffffffL)
+    return fail(SAMPT_ERR_ARG, "sampt_prompt_fill: n_items and ld must be positive and n_items * ld * 2 below 2^31; got n_items = " +
+                                   std::to_string(n_items) + ", ld = " + std::to_string(ld));
+  if (!traj || !vis || !items || !pts || !labels || !k_item || !npos_item) return fail(SAMPT_ERR_ARG, "sampt_prompt_fill: null pointer");
+  return prompt_fill(traj, vis, T, M, P, pp, negatives, add_others, sx, sy, (const int*)items, n_items, ld, pts, (int*)labels, (int*)k_item,
+                     (int*)npos_item, (hipStream_t)stream);
+}
+
+int sampt_mark_outside_frame(const float* traj, const float* vis_in, long n, int H, int W, float* vis_out, sampt_stream_t stream) {
+  if (n <= 0 || H <= 0 || W <= 0)
+    return fail(SAMPT_ERR_ARG, "sampt_mark_outside_frame: n, H and W must be positive; got n = " + std::to_string(n) + ", H = " +
+                                   std::to_string(H) + ", W = " + std::to_string(W));
+  if (!traj || !vis_in || !vis_out) return fail(SAMPT_ERR_ARG, "sampt_mark_outside_frame: null pointer");
+  return mark_outside_frame(traj, vis_in, n, H, W, vis_out, (hipStream_t)stream);
+}
+
 int sampt_viz_compose(const uint8_t* frames, int interleaved, int n_frames, int h, int w, const uint64_t* bits, const uint64_t* band,
                       int n_masks, const uint8_t* lut, const int32_t* markers, int n_markers, int panel, uint8_t* out,
                       sampt_stream_t stream) {

@@ -458,6 +458,14 @@ int viz_compose(const unsigned char* frames, int interleaved, int n_frames, int 
 int patch_filter(const unsigned char* rgb, int T, int H, int W, const float* query, const float* traj, const float* vis_in, int N,
                  int patch_size, float threshold, const double* companding, int border_rule, float* vis_out, float* sim_out,
                  hipStream_t s);
+// ---- prompt_assembly.hip: SamPt._prepare_points + apply_coords per (frame, object) item from tracks on the device.  traj f32
+// [T][M][P][2], vis f32 [T][M][P] codes (visible iff == 1).  prompt_count: k_all / npos_all int [T * M].  prompt_fill: the F items
+// named by items (int, item = t * M + m) -> pts f32 [F][ld][2], labels int [F][ld] (zeros past an item's k), k_item / npos_item int [F].
+// mark_outside_frame: vis_out[i] = -2 where point i of traj [n][2] fails one of the four border comparisons, else vis_in[i] (may alias).
+int prompt_count(const float* vis, int T, int M, int P, int pp, int negatives, int add_others, int* k_all, int* npos_all, hipStream_t s);
+int prompt_fill(const float* traj, const float* vis, int T, int M, int P, int pp, int negatives, int add_others, double sx, double sy,
+                const int* items, int F, int ld, float* pts, int* labels, int* k_item, int* npos_item, hipStream_t s);
+int mark_outside_frame(const float* traj, const float* vis_in, long n, int H, int W, float* vis_out, hipStream_t s);
 int bbox_from_logits_state(const float* logits, int h, int w, int* bbox_state, int* bbox_partial, hipStream_t s);
 // mask-input embedding (PromptEncoder.mask_downscaling, App. A-4) fused with "src = image_embedding + dense":
 //   mask (4g x 4g) -> conv2x2s2(1->c1) LN2d GELU -> conv2x2s2(c1->c2) LN2d GELU -> conv1x1(c2->256) ; src = feat + dense

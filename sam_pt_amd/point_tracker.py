@@ -121,9 +121,24 @@ class _EngineTracker(PointTracker, _lib.EngineOwner):
     """A tracker over one native engine ``_h``: a subclass names ``_engines`` and itself (``_who``, for messages) and packs + creates in ``_build(lib, device)``."""
     _h = None
     _device = None
+    # True: ``evaluate_batch`` leaves trajectories_pred / visibilities_pred / query_points where ``forward`` produced them (HIP
+    # tensors) instead of the reference's CPU copies (tracker.py:82-83).  ``SamPt(device_tracks=True)`` sets it around its calls.
+    results_on_device = False
 
     def _ensure(self, device: torch.device):
         self.ensure_engines(device, self._who, self._build)
+
+    def evaluate_batch(self, rgbs, query_points, trajectories_gt=None, visibilities_gt=None):
+        if not self.results_on_device:
+            return super().evaluate_batch(rgbs, query_points, trajectories_gt, visibilities_gt)
+        traj, vis = self.forward(rgbs, query_points)
+        assert traj.shape == (rgbs.shape[0], rgbs.shape[1], query_points.shape[1], 2)
+
+        def cpu(t):                                  # the ground-truth pass-throughs stay CPU copies, as in the reference
+            return t.detach().clone().cpu() if t is not None else None
+
+        return {"trajectories_pred": traj, "visibilities_pred": vis, "query_points": query_points,
+                "trajectories_gt": cpu(trajectories_gt), "visibilities_gt": cpu(visibilities_gt)}
 
 
 class _ClipTracker(_EngineTracker):

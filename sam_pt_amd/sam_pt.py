@@ -6,8 +6,12 @@ The reference drives its predictor one call at a time with a host round trip aft
 
   * frames stay on the device; the whole clip is image-encoded in batches (``SamPredictor.encode_frames``) and the
     embeddings stay in HBM;
-  * all prompts of the clip are assembled once on the host (the trajectories arrive on the CPU anyway —
-    point_tracker/tracker.py:82-83) and uploaded in one copy;
+  * all prompts of the clip are assembled once on the host (the reference's tracker contract hands the trajectories over as
+    CPU copies — point_tracker/tracker.py:82-83) and uploaded in one copy per chunk; with ``SamPt(..., device_tracks=True)`` the
+    engine trackers leave their results on the device instead (``results_on_device``), the border rule and the prompts are
+    computed there (csrc/prompt_assembly.hip, specified by ``sam_pt_amd/prompt_assembly.py``) and only 2 * T * M point counts
+    come to the host for its decisions; the returned trajectories / visibilities are CPU tensors either way
+    (``SamPt._device_tracks_active`` lists what keeps the host path);
   * each (frame, object) runs ``SamPredictor.track_decode``: the 1-2 prompt passes + R refinement passes +
     IoU-threshold rejection of ``predict_mask`` (sam_pt.py:760-837) as one device-side chain without host syncs.
 
@@ -22,7 +26,7 @@ Shi-Tomasi / "mixed" point selection restate OpenCV's algorithms on the host (pa
 The optional patch-similarity filter (sam_pt.py:597-682, off in every shipped config) is built twice: on the host with a
 restated ``rgb2lab`` (skimage absent: that one function is parity unpinned), which is what runs on CPU tensors, and as one
 HIP launch (``sam_pt_amd/patch_filter.py``, held to the host restatement), which is what runs when the tracker's results are
-HIP tensors.
+HIP tensors — with ``device_tracks=True`` those of every engine tracker.
 """
 from __future__ import annotations
 
@@ -99,8 +103,12 @@ class SamPt(nn.Module):
                  iterative_refinement_iterations: int = 12, use_patch_matching_filtering: bool = False,
                  patch_size: int = 3, patch_similarity_threshold: float = 0.01, use_point_reinit: bool = False,
                  reinit_point_tracker_horizon: int = 24, reinit_horizon: int = 24,
-                 reinit_variant: str = "reinit-at-median-of-area-diff"):
+                 reinit_variant: str = "reinit-at-median-of-area-diff", device_tracks: bool = False):
         super().__init__()
+        # device_tracks (not a keyword of the reference; off by default): on the fused path the point tracks stay on the device and the
+        # prompts are assembled there (sam_pt_amd/prompt_assembly.py) — see ``_device_tracks_active`` for when the mode applies
+        self.device_tracks = bool(device_tracks)
+        self._count_stream = None
         self.point_tracker = point_tracker
         self.sam_predictor = sam_predictor
         self.sam_iou_threshold = sam_iou_threshold
@@ -229,6 +237,8 @@ class SamPt(nn.Module):
         else:                                                            # demo (sam_pt.py:178-182)
             query_points = video["query_points"]
         tracked = None
+        dev_tracks = self._device_tracks_active(images, frame_ids)
+        tracks_ready = None
         if fused:
             limit = getattr(self.sam_predictor, "max_prompt_points", None)
             if limit is not None:        # fail before the clip is encoded, not after (the reference accepts any prompt size)
@@ -299,7 +309,10 @@ class SamPt(nn.Module):
                 with torch.cuda.stream(self._side_stream):
                     if hasattr(self.point_tracker, "prepare") and self.overlap_tracker_encoder_fnet:
                         self.point_tracker.to(self.device).prepare(images)
-                    tracked = self._track_points(images, query_points)
+                    tracked = self._track_points(images, query_points, on_device=dev_tracks)
+                    if dev_tracks:                # the SAM stage (another stream) reads the tracks on the device: its ordering point
+                        tracks_ready = torch.cuda.Event()
+                        tracks_ready.record()
                     self._mark("tracked")
                 torch.cuda.current_stream().wait_stream(self._side_stream)
                 if enc_stream is not None:
@@ -345,24 +358,27 @@ class SamPt(nn.Module):
                     "trajectories": trajectories, "visibilities": visibilities}
 
         if not self.use_point_reinit:
-            trajectories, visibilities = tracked if tracked is not None else self._track_points(images, query_points)
+            trajectories, visibilities = tracked if tracked is not None else self._track_points(images, query_points, on_device=dev_tracks)
             pl = pipeline if fused else None
             if frame_ids is None:
                 sam_args = (images, trajectories, visibilities)
             else:
                 ids = torch.as_tensor(frame_ids)
                 sam_args = (sam_images, trajectories[ids], visibilities[ids])
+            kw = {"tracks_ready": tracks_ready} if dev_tracks else {}
             if defer and pl is not None:     # forward_begin: the decoder chain is enqueued, nobody waits for it yet
-                pend = self._apply_sam_to_trajectories(*sam_args, feats, pl, defer=True)
+                pend = self._apply_sam_to_trajectories(*sam_args, feats, pl, defer=True, **kw)
 
                 def complete():
                     _, logits, scores_per_frame = self._finish_sam_fused(pend)
                     self._mark("decoded")
-                    return tail(trajectories, visibilities, logits, scores_per_frame.mean(dim=0), scores_per_frame)
+                    # (device_tracks: the tracks come home here, once — the count download has long waited for the tracker)
+                    return tail(trajectories.cpu(), visibilities.cpu(), logits, scores_per_frame.mean(dim=0), scores_per_frame)
                 return PendingForward(complete)
-            _, logits, scores_per_frame = self._apply_sam_to_trajectories(*sam_args, feats, pl)
+            _, logits, scores_per_frame = self._apply_sam_to_trajectories(*sam_args, feats, pl, **kw)
             scores = scores_per_frame.mean(dim=0)
             self._mark("decoded")
+            trajectories, visibilities = trajectories.cpu(), visibilities.cpu()      # (device_tracks: copied once, at the end)
         else:
             trajectories, visibilities, logits, scores, scores_per_frame = self._forward_w_reinit(images, query_points, feats)
         return tail(trajectories, visibilities, logits, scores, scores_per_frame)
@@ -549,8 +565,23 @@ class SamPt(nn.Module):
             feats=sub_feats)
         return (logits > self.sam_predictor.model.mask_threshold)[0]
 
-    def _track_points(self, rgbs, query_points):
-        """Chunks of ``point_tracker_mask_batch_size`` objects per tracker call (sam_pt.py:545-576, 578-692)."""
+    def _device_tracks_active(self, images, frame_ids=None) -> bool:
+        """Whether this clip runs with ``device_tracks``: tracker results left on the device (``results_on_device``), border rule
+        and prompt assembly there (sam_pt_amd/prompt_assembly.py), one download of 2 * T * M counts in place of the trajectories'.
+        Everything else takes the host path, silently: ``use_point_reinit`` (the re-initialisation loop reads masks and tracks on
+        the host), a tracker with ``set_masks`` (SuperGlue: runs after the encoder, on host-side masks) or without
+        ``results_on_device`` (not an engine tracker), ``max_other_objects_positive_points`` (its ``np.random.choice`` is host RNG),
+        a predictor without ``encode_frames`` / ``track_decode``, frames that are not on a HIP device, and ``video["frame_ids"]``
+        (frame sharding selects the SAM stage's frames from the whole clip's tracks on the host)."""
+        pred = self.sam_predictor
+        return bool(self.device_tracks and hasattr(pred, "encode_frames") and hasattr(pred, "track_decode")
+                    and not self.use_point_reinit and not hasattr(self.point_tracker, "set_masks")
+                    and hasattr(self.point_tracker, "results_on_device") and self.max_other_objects_positive_points is None
+                    and frame_ids is None and bool(getattr(images, "is_cuda", False)))
+
+    def _track_points(self, rgbs, query_points, on_device=False):
+        """Chunks of ``point_tracker_mask_batch_size`` objects per tracker call (sam_pt.py:545-576, 578-692).  ``on_device``
+        (``device_tracks``): the tracker leaves its results on the device, the border rule runs there, the chunks are joined there."""
         trajs, viss = [], []
         n_masks = query_points.shape[0]
         rgbs_dev = rgbs.to(self.device).unsqueeze(0)
@@ -558,12 +589,24 @@ class SamPt(nn.Module):
         for i in range(0, n_masks, self.point_tracker_mask_batch_size):
             q = query_points[i:i + self.point_tracker_mask_batch_size]
             m, p, _ = q.shape
-            with torch.no_grad():
-                out = self.point_tracker.to(self.device).evaluate_batch(rgbs_dev, q.reshape(1, m * p, 3).to(self.device))
+            tracker = self.point_tracker.to(self.device)
+            keep = getattr(tracker, "results_on_device", False)
+            try:
+                if on_device:
+                    tracker.results_on_device = True
+                with torch.no_grad():
+                    out = tracker.evaluate_batch(rgbs_dev, q.reshape(1, m * p, 3).to(self.device))
+            finally:
+                if on_device:
+                    tracker.results_on_device = keep
             t = out["trajectories_pred"].squeeze(0)
             v = out["visibilities_pred"].squeeze(0).float()
             hw = rgbs.shape[-2:]
-            if self.use_patch_matching_filtering and t.is_cuda and self.patch_filter_on_device:
+            if on_device and t.is_cuda and not self.use_patch_matching_filtering:
+                # the four border comparisons in one launch (with the filter they are part of ITS launch, below)
+                from .prompt_assembly import mark_outside_frame
+                v = mark_outside_frame(t, v, *hw)
+            elif self.use_patch_matching_filtering and t.is_cuda and self.patch_filter_on_device:
                 # a tracker that leaves its results on the HIP device: filter and border rule in one launch, on the frames as they
                 # stand in rgbs_dev (sam_pt_amd/patch_filter.py)
                 from .patch_filter import patch_similarity_filter
@@ -654,26 +697,34 @@ class SamPt(nn.Module):
             labels = np.concatenate([labels, np.zeros((len(others)), dtype=int)], axis=0)
         return coords, labels
 
-    def _apply_sam_to_trajectories(self, images, trajectories, visibilities, feats=None, pipeline=None, defer=False):
+    def _apply_sam_to_trajectories(self, images, trajectories, visibilities, feats=None, pipeline=None, defer=False,
+                                   tracks_ready=None):
+        """``tracks_ready`` (``device_tracks``): the tracks are HIP tensors and stay there — the event after which they may be read
+        (None: they are ordered before the current stream's position)."""
         n_frames, channels, height, width = images.shape
         _, n_masks, points_per_mask, _ = trajectories.shape
         assert trajectories.shape == (n_frames, n_masks, points_per_mask, 2)
         assert visibilities.shape == (n_frames, n_masks, points_per_mask)
-        trajectories, visibilities = trajectories.cpu(), visibilities.cpu()
+        on_device = self._device_tracks_active(images) and feats is not None and trajectories.is_cuda and visibilities.is_cuda
+        if not on_device:
+            trajectories, visibilities = trajectories.cpu(), visibilities.cpu()
         if feats is not None:
+            if on_device and tracks_ready is None:
+                tracks_ready = torch.cuda.Event()
+                tracks_ready.record()
             if pipeline is None:
-                return self._apply_sam_fused(images, trajectories, visibilities, feats)
+                return self._apply_sam_fused(images, trajectories, visibilities, feats, tracks_ready=tracks_ready)
             events, stream = pipeline
             with torch.cuda.stream(stream):       # everything of the SAM stage is allocated and launched on `stream`
-                pend = self._enqueue_sam_fused(images, trajectories, visibilities, feats, events)
+                pend = self._enqueue_sam_fused(images, trajectories, visibilities, feats, events, tracks_ready)
                 pend["event"] = torch.cuda.Event()
                 pend["event"].record()            # this clip's chain (and the copy of its scores to the host) ends here
             return pend if defer else self._finish_sam_fused(pend)
         return self._apply_sam_stepwise(images, trajectories, visibilities)
 
     # -- device-resident path --------------------------------------------------------------------------------
-    def _apply_sam_fused(self, images, trajectories, visibilities, feats, batch_events=None):
-        return self._finish_sam_fused(self._enqueue_sam_fused(images, trajectories, visibilities, feats, batch_events))
+    def _apply_sam_fused(self, images, trajectories, visibilities, feats, batch_events=None, tracks_ready=None):
+        return self._finish_sam_fused(self._enqueue_sam_fused(images, trajectories, visibilities, feats, batch_events, tracks_ready))
 
     def _finish_sam_fused(self, pend):
         """Second half of the SAM stage: wait for the chain enqueued by ``_enqueue_sam_fused`` (its own event when it ran on a
@@ -690,8 +741,10 @@ class SamPt(nn.Module):
         scores_cpu = (pend["host"].clone() if pend["host"] is not None else scores.cpu()).view(pend["n_frames"], pend["n_masks"])
         return self._mean_scores(scores_cpu), logits, scores_cpu
 
-    def _enqueue_sam_fused(self, images, trajectories, visibilities, feats, batch_events=None):
+    def _enqueue_sam_fused(self, images, trajectories, visibilities, feats, batch_events=None, tracks_ready=None):
         """First half: prompts assembled on the host, every decoder chain of the clip enqueued on the current stream.
+        With tracks on the device (``device_tracks``; ``tracks_ready``: the event after which they may be read) only every item's
+        point counts come to the host, the same decisions are taken from them and each chunk's prompts are written on the device.
         ``batch_events``: [(end_frame, event)] of the encoder batches (``SamPredictor.encode_frames``).  When given, the
         current stream is a decoder stream that must not wait for the whole encoder: the items are chunked per encoder
         batch and every chunk waits only for the event of the batch that holds its frames."""
@@ -700,30 +753,38 @@ class SamPt(nn.Module):
         dev = self.device
         pred = self.sam_predictor
         size = (height, width)
-        prompts = []
-        kmax = 1
-        traj_np, vis_np = trajectories.numpy(), (visibilities == 1).numpy()
-        for t in range(n_frames):
-            for m in range(n_masks):
-                c, l = self._prepare_points(traj_np, vis_np, t, m, n_masks)
-                if len(c):
-                    c = pred.transform.apply_coords(c, size)
-                prompts.append((c, l))
-                kmax = max(kmax, len(c))
+        on_device = trajectories.is_cuda
+        if on_device:
+            k_all, npos_all = self._prompt_counts_on_device(trajectories, visibilities, tracks_ready)
+            new_h, new_w = pred.transform.get_preprocess_shape(height, width, pred.transform.target_length)
+            # what sampt_prompt_fill needs besides the tracks; the last two are apply_coords' float64 factors
+            asm = (self.positive_points_per_mask, self.negative_points_per_mask > 0,
+                   self.add_other_objects_positive_points_as_negative_points, new_w / width, new_h / height)
+        else:
+            prompts = []
+            traj_np, vis_np = trajectories.numpy(), (visibilities == 1).numpy()
+            for t in range(n_frames):
+                for m in range(n_masks):
+                    c, l = self._prepare_points(traj_np, vis_np, t, m, n_masks)
+                    if len(c):
+                        c = pred.transform.apply_coords(c, size)
+                    prompts.append((c, l))
+            k_all = np.array([len(c) for c, _ in prompts], dtype=np.int32)
+            npos_all = np.array([int((l == 1).sum()) for _, l in prompts], dtype=np.int32)
+        kmax = max(1, int(k_all.max())) if len(k_all) else 1
         use_graph = bool(getattr(pred, "use_graph", False)) and hasattr(pred, "decode_staging") and images.is_cuda
         if use_graph:        # point slots in steps of 8: clips whose longest prompts differ by a point share their staging
             kmax = -(-kmax // 8) * 8     # buckets and captured graphs (the slots past an item's count are never read)
-        xy = np.zeros((len(prompts), kmax, 2), dtype=np.float32)
-        lab = np.zeros((len(prompts), kmax), dtype=np.int32)
-        for i, (c, l) in enumerate(prompts):
-            xy[i, :len(c)] = c
-            lab[i, :len(c)] = l
+        if not on_device:
+            xy = np.zeros((len(prompts), kmax, 2), dtype=np.float32)
+            lab = np.zeros((len(prompts), kmax), dtype=np.int32)
+            for i, (c, l) in enumerate(prompts):
+                xy[i, :len(c)] = c
+                lab[i, :len(c)] = l
         # All (frame, object) items with a non-empty prompt run as ONE batched device-side chain per chunk of Fmax items,
         # whatever their number of visible points: the batch is ragged (per-item point counts, padding tokens masked in
         # the decoder's attention), so an item's result equals its un-batched one.
-        items = [i for i, (c, l) in enumerate(prompts) if len(c) > 0]            # empty prompt: sam_pt.py:766-767
-        k_all = np.array([len(c) for c, _ in prompts], dtype=np.int32)
-        npos_all = np.array([int((l == 1).sum()) for _, l in prompts], dtype=np.int32)
+        items = np.nonzero(k_all > 0)[0].tolist()                                 # empty prompt: sam_pt.py:766-767
         two_pass = self.negative_points_per_mask > 0
         # (a TinyViT predictor asks for chains of one item, SamHip.clip_decode_batch: its clip path equals predict_torch bit for bit)
         Fmax = getattr(pred.model, "clip_decode_batch", None) or getattr(pred.model, "max_decode_batch", 1)
@@ -744,7 +805,7 @@ class SamPt(nn.Module):
             # every output element is written by exactly one item; only items WITHOUT a prompt keep the -inf the reference gives them
             logits = torch.empty((n_masks, n_frames, height, width), dtype=torch.float32, device=dev)
             scores = torch.empty((n_frames * n_masks,), dtype=torch.float32, device=dev)
-            if len(items) < len(prompts):
+            if len(items) < n_frames * n_masks:
                 _lib.check(lib.sampt_fill_f32(_lib.ptr(logits), logits.numel(), -float("inf"), _lib.stream_ptr()), "sampt_fill_f32")
                 _lib.check(lib.sampt_fill_f32(_lib.ptr(scores), scores.numel(), -float("inf"), _lib.stream_ptr()), "sampt_fill_f32")
             # A chunk's prompts are packed on the host, in chunk order, straight into a pinned mirror of its bucket's device block and
@@ -759,16 +820,25 @@ class SamPt(nn.Module):
                 if mir["free"] is not None:
                     mir["free"].synchronize()              # the previous clip's copy out of this mirror (long done; never waits)
                 ch = np.asarray(chunk, dtype=np.int64)
-                mir["pts"][...] = xy[ch]
-                mir["labels"][...] = lab[ch]
-                mir["k"][...] = k_all[ch]
-                mir["npos"][...] = npos_all[ch]
+                if not on_device:          # (on the device only the item numbers cross: sampt_prompt_fill writes the rest of the block)
+                    mir["pts"][...] = xy[ch]
+                    mir["labels"][...] = lab[ch]
+                    mir["k"][...] = k_all[ch]
+                    mir["npos"][...] = npos_all[ch]
                 mir["items"][...] = ch
                 staged.append((st, mir))
         else:
-            xy_d = torch.from_numpy(xy).to(dev)
-            lab_d = torch.from_numpy(lab).to(dev)
-            k_d, npos_d = torch.from_numpy(k_all).to(dev), torch.from_numpy(npos_all).to(dev)
+            if on_device:                  # every item's prompt in one launch, into the tensors the chunks select from
+                from .prompt_assembly import fill_prompts
+                n_all = n_frames * n_masks
+                xy_d = torch.empty((n_all, kmax, 2), dtype=torch.float32, device=dev)
+                lab_d = torch.empty((n_all, kmax), dtype=torch.int32, device=dev)
+                k_d, npos_d = torch.empty((n_all,), dtype=torch.int32, device=dev), torch.empty((n_all,), dtype=torch.int32, device=dev)
+                fill_prompts(trajectories, visibilities, *asm, torch.arange(n_all, dtype=torch.int32, device=dev), xy_d, lab_d, k_d, npos_d)
+            else:
+                xy_d = torch.from_numpy(xy).to(dev)
+                lab_d = torch.from_numpy(lab).to(dev)
+                k_d, npos_d = torch.from_numpy(k_all).to(dev), torch.from_numpy(npos_all).to(dev)
             logits = torch.full((n_masks, n_frames, height, width), -float("inf"), dtype=torch.float32, device=dev)
             scores = torch.full((n_frames * n_masks,), -float("inf"), dtype=torch.float32, device=dev)
             idx_d = [torch.tensor(chunk, dtype=torch.long, device=dev) for chunk, _ in chunks]
@@ -784,7 +854,12 @@ class SamPt(nn.Module):
                 st, mir = staged[ci]
                 # (the bucket's device block is shared by the chunks that use it: filled here, in stream order, from the chunk's own
                 #  pinned mirror — an asynchronous copy, the host does not wait for the encoder)
-                st["block"].copy_(mir["host"], non_blocking=True)
+                if on_device:              # the item numbers from the mirror's tail, the prompts from the tracks where they are
+                    from .prompt_assembly import fill_prompts
+                    st["items"].copy_(mir["host"][-F_:], non_blocking=True)
+                    fill_prompts(trajectories, visibilities, *asm, st["items"], st["pts"], st["labels"], st["k_item"], st["npos_item"])
+                else:
+                    st["block"].copy_(mir["host"], non_blocking=True)
                 mir["free"] = torch.cuda.Event()
                 mir["free"].record()
                 emb, hq = (feats.emb, feats.hq) if hasattr(feats, "emb") else (feats, None)
@@ -822,6 +897,29 @@ class SamPt(nn.Module):
             host.copy_(scores, non_blocking=True)
         return {"logits": logits, "scores": scores, "host": host, "n_frames": n_frames, "n_masks": n_masks, "event": None,
                 "feats": feats}                    # (the embeddings stay referenced until the chain that reads them is done)
+
+    def _prompt_counts_on_device(self, trajectories, visibilities, tracks_ready):
+        """Every item's prompt length and positive count (numpy int32 (T*M,) each) from visibilities on the device: one launch, one
+        copy of 2 * T * M ints into pinned memory and the SAM stage's one wait for the tracker.  They run on a stream of their own
+        behind ``tracks_ready``, so the wait is for the tracker only — not for the encoder, nor for an earlier clip's chains on the
+        decoder stream (``forward_begin``); the current stream is ordered behind the tracks for the fills that follow."""
+        from .prompt_assembly import count_prompts
+        dev = visibilities.device
+        if self._count_stream is None or self._count_stream.device != dev:
+            self._count_stream = torch.cuda.Stream(device=dev)
+        cs, cur = self._count_stream, torch.cuda.current_stream(dev)
+        cs.wait_event(tracks_ready)
+        host = torch.empty((2, visibilities.shape[0] * visibilities.shape[1]), dtype=torch.int32, pin_memory=True)
+        with torch.cuda.stream(cs):
+            counts = count_prompts(visibilities, self.positive_points_per_mask, self.negative_points_per_mask > 0,
+                                   self.add_other_objects_positive_points_as_negative_points)
+            host.copy_(counts, non_blocking=True)
+        cs.synchronize()
+        cur.wait_event(tracks_ready)
+        visibilities.record_stream(cs)
+        trajectories.record_stream(cur)
+        visibilities.record_stream(cur)
+        return host[0].numpy(), host[1].numpy()
 
     @staticmethod
     def _mean_scores(scores_per_frame):
