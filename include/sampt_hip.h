@@ -716,6 +716,20 @@ int sampt_rle_decode_bits(const uint32_t* counts_dev, const int64_t* offsets_dev
                           uint64_t* bits_out_dev, int32_t* area_out_dev, int32_t* status_out_dev, void* workspace_dev,
                           size_t workspace_bytes, sampt_stream_t stream);
 int sampt_bits_unpack(const uint64_t* bits_dev, int n, int h, int w, uint8_t* bytes_out_dev, sampt_stream_t stream);
+/* Rank -> pixel on bit-planes (csrc/mask_points.hip): "the r-th set pixel of this mask, in nonzero() order", so that a host that knows
+ * only a mask's area can draw ranks and the pixels stay on the device (query-point selection, sam_pt_amd/query_points.py).  Integer
+ * work only, no atomics, stream-ordered; equal to the host restatement of sam_pt_amd/mask_points.py.
+ * bits_row_prefix: bits_dev holds n planes in the format of sampt_bits_pack (8-byte aligned).  prefix_out_dev int32 [n][h + 1]:
+ *   prefix[i][y] = the set pixels of plane i in rows < y, so prefix[i][0] = 0 and prefix[i][h] = the plane's area.  The complement's
+ *   prefix is not stored: it is y * w - prefix[i][y].  n = 0 is a no-op.
+ * bits_select: prefix_dev as written by bits_row_prefix for the same planes.  queries_dev int32 [nq][3] = (plane, invert, rank);
+ *   yx_out_dev f32 [nq][2] receives ((float) y, (float) x) of the rank-th pixel, 0-based, in row-major order - mask.nonzero()[rank] -
+ *   counting set pixels, or with invert != 0 the clear pixels inside the image (rows >= h and columns >= w never count).  A query whose
+ *   plane is outside [0, n) or whose rank is outside [0, area) (inverted: [0, h * w - area)) gives (-1, -1) and reads nothing out of
+ *   bounds.  Queries are independent: any order, any mix of planes and polarities in one launch.  nq = 0 and n = 0 are no-ops. */
+int sampt_bits_row_prefix(const uint64_t* bits_dev, int n, int h, int w, int32_t* prefix_out_dev, sampt_stream_t stream);
+int sampt_bits_select(const uint64_t* bits_dev, const int32_t* prefix_dev, int n, int h, int w, const int32_t* queries_dev, int nq,
+                      float* yx_out_dev, sampt_stream_t stream);
 size_t sampt_seq_iou_workspace_bytes(int n_dt, int n_gt, int n_frames, int h, int w);
 int sampt_seq_iou_counts(const uint64_t* dt_bits_dev, const int32_t* dt_area_dev, const int32_t* dt_planes_dev, int n_dt, int dt_n_planes,
                          const uint64_t* gt_bits_dev, const int32_t* gt_area_dev, const int32_t* gt_planes_dev, int n_gt, int gt_n_planes,

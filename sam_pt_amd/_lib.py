@@ -167,6 +167,8 @@ _SIGS = {
     "sampt_rle_decode_workspace_bytes": (c_size_t, [C.c_int64]),
     "sampt_rle_decode_bits": (c_int, [_P, _P, c_int, C.c_int64, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "sampt_bits_unpack": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
+    "sampt_bits_row_prefix": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
+    "sampt_bits_select": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_int, _P, _P]),
     "sampt_seq_iou_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "sampt_seq_iou_counts": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "sampt_vis_match": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -1188,6 +1188,22 @@ int sampt_bits_unpack(const uint64_t* bits, int n, int h, int w, uint8_t* bytes_
   return rc;
 }
 
+int sampt_bits_row_prefix(const uint64_t* bits, int n, int h, int w, int32_t* prefix_out, sampt_stream_t stream) {
+  if (ve_bad_shape("sampt_bits_row_prefix", n, h, w) != SAMPT_OK) return SAMPT_ERR_ARG;
+  int rc = bits_row_prefix((const unsigned long long*)bits, n, h, w, (int*)prefix_out, (hipStream_t)stream);
+  if (rc == SAMPT_ERR_ARG) return fail(rc, "sampt_bits_row_prefix: null or misaligned pointer");
+  return rc;
+}
+
+int sampt_bits_select(const uint64_t* bits, const int32_t* prefix, int n, int h, int w, const int32_t* queries, int nq, float* yx_out,
+                      sampt_stream_t stream) {
+  if (ve_bad_shape("sampt_bits_select", n, h, w) != SAMPT_OK) return SAMPT_ERR_ARG;
+  if (nq < 0) return fail(SAMPT_ERR_ARG, "sampt_bits_select: negative number of queries");
+  int rc = bits_select((const unsigned long long*)bits, (const int*)prefix, n, h, w, (const int*)queries, nq, yx_out, (hipStream_t)stream);
+  if (rc == SAMPT_ERR_ARG) return fail(rc, "sampt_bits_select: null or misaligned pointer");
+  return rc;
+}
+
 size_t sampt_seq_iou_workspace_bytes(int n_dt, int n_gt, int n_frames, int h, int w) {
   return seq_iou_workspace_bytes(n_dt, n_gt, n_frames, h, w);
 }

@@ -442,6 +442,12 @@ int seq_iou_counts(const unsigned long long* dt_bits, const int* dt_area, const 
                    long long* counts, void* ws, size_t ws_bytes, hipStream_t s);
 int vis_match(const long long* counts, int D, int G, int A, int n_thr, const double* thrs, const int* gt_order, const unsigned char* gt_ignore,
               const unsigned char* iscrowd, const unsigned char* dt_out, int* dt_match, int* gt_match, unsigned char* dt_ignore, hipStream_t s);
+// ---- mask_points.hip: rank -> pixel on bit-planes.  bits_row_prefix: prefix int [n][h + 1], prefix[i][y] = set pixels of plane i in
+// rows < y.  bits_select: queries int [nq][3] = (plane, invert, rank) -> yx f32 [nq][2], the rank-th set (invert: clear, inside the
+// image) pixel in row-major order, (-1, -1) for a plane or rank out of range.
+int bits_row_prefix(const unsigned long long* bits, int n, int h, int w, int* prefix, hipStream_t s);
+int bits_select(const unsigned long long* bits, const int* prefix, int n, int h, int w, const int* queries, int nq, float* yx_out,
+                hipStream_t s);
 // ---- viz.hip: prediction overlays.  viz_band: bit-planes [n][nb][w] -> the contour band dil(m) & dil(~m) in the same layout (disk of
 // radius 0 .. 64, ~m inside the image only).  viz_compose: frames uint8 [T][3][h][w] (or interleaved [T][h][w][3]) -> out [T][h][w][3],
 // or [T][2 h][w][3] for panel 3; panel bit 0 = the input panel (frame + markers), bit 1 = the predictions panel (frame, per mask the

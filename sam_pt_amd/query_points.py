@@ -19,6 +19,9 @@ Needed by ``SamPt`` in ``query_masks`` mode (every VOS run, sam_pt.py:171-177) a
   unpinned** against OpenCV itself (the erosion is pinned on ``scipy.ndimage.binary_erosion`` and the min-eigenvalue map
   cross-checked against ``scipy.ndimage`` filters, tests/test_cpu_host.py).  With a HIP device the whole corner selection runs
   there (``shi_tomasi_device``, csrc/corners.hip), bit-identical to the numpy restatement.
+* ``select_query_points`` — the selectors above in two steps, "which ranks" (host, the same draws in the same order) and "which
+  pixels" (a source: ``mask_points.HostMasks``, or ``mask_points.DevicePlanes`` for masks that stay on the device as bit-planes,
+  csrc/mask_points.hip).  What ``SamPt(device_reinit=True)`` runs; the functions above stay the specification and the host path.
 """
 from __future__ import annotations
 
@@ -65,7 +68,8 @@ def kmedoids_alternate(X: np.ndarray, n_clusters: int, max_iter: int = 300) -> n
 
 def kmedoids_alternate_device(X: torch.Tensor, n_clusters: int, device, max_iter: int = 300) -> np.ndarray:
     """``kmedoids_alternate`` on the HIP device, bit-identical to the host restatement (csrc/kmedoids.hip: fp64 distances, numpy's
-    pairwise summation order, first-index ties).  X: (n, 2) float32 pixel coordinates on the host, n <= 2048.  The heuristic
+    pairwise summation order, first-index ties).  X: (n, 2) float32 pixel coordinates, n <= 2048, on the host or already on
+    ``device`` (a subsample that ``sampt_bits_select`` wrote there is read where it lies: no upload).  The heuristic
     initialisation's ``np.argpartition`` stays on the host (its output order is numpy's introselect): the device returns the row
     sums, the host partitions n doubles, the device iterates to convergence — two small round trips instead of 60 - 160 ms of
     numpy on an n x n fp64 matrix."""
@@ -299,6 +303,134 @@ def extract_mixed_points(query_masks, query_points_timestep, images, n_points: i
     if len(parts) == 1:
         return parts[0]
     return [torch.cat(x, dim=0) for x in zip(*parts)]
+
+
+# ---- the selectors above in two steps: which RANKS (host, RNG) and which PIXELS (a source of pixels: mask_points.HostMasks reads
+# nonzero() on the host, mask_points.DevicePlanes asks csrc/mask_points.hip) -------------------------------------------------------------
+# The functions above are the specification: for the same seed ``select_query_points`` returns their points with ``==`` and leaves
+# the global generator in the same state (tests/test_mask_points_cpu.py), because the rank step makes their draws in their order —
+# all positives of all masks, then all negatives; within ``mixed`` the k-medoid share of every mask, then the Shi-Tomasi top-ups,
+# then the random share — and a draw needs nothing of a mask but its area.
+def rank_step(area: int, n_points_to_select: int, cut: int = None):
+    """The ranks (into ``mask.nonzero()``) that a selector reads from a mask of ``area`` pixels: None for an empty mask (no draw),
+    ``i % area`` when there are fewer pixels than points (no draw), else one ``torch.randperm(area)`` on the global generator, cut
+    to ``cut`` (k-medoids: the subsample size) or to the number of points."""
+    if area == 0:
+        return None
+    if area < n_points_to_select:
+        return torch.arange(n_points_to_select) % area
+    return torch.randperm(area)[:n_points_to_select if cut is None else cut]
+
+
+def shi_tomasi_host(image: torch.Tensor, mask: torch.Tensor, n_points: int) -> torch.Tensor:
+    """The Shi-Tomasi half of ``extract_corner_points`` on the host (its erosion cascade and ``good_features_to_track``, without the
+    k-medoid top-up): image (3,H,W) uint8, non-empty mask (H,W) {0,1} -> (n_found <= n, 2) float32 (x, y)."""
+    img = image.permute(1, 2, 0).cpu().numpy()
+    eroded = erode_mask_proportional_to_its_furthest_points_distance(mask, 0.06)
+    for pct in (0.02, 0.01):
+        if eroded.sum() < 10:
+            eroded = erode_mask_proportional_to_its_furthest_points_distance(mask, pct)
+    if eroded.sum() < 10:
+        eroded = mask
+    px = eroded.nonzero().float()
+    diameter = torch.norm(px.max(0)[0] - px.min(0)[0]).item()
+    corners = good_features_to_track(_rgb_to_gray_u8(img), n_points, 0.001, diameter / n_points, eroded.cpu().numpy().astype(np.uint8))
+    return torch.from_numpy(corners).type(torch.float32)
+
+
+def method_shares(method: str, n_points: int):
+    """[(selector, points)] of a selection method, in the order the points are returned (``extract_query_points_xy`` /
+    ``extract_mixed_points``)."""
+    if method in ("kmedoids", "random"):
+        return [(method, n_points)]
+    if method == "shi-tomasi":
+        return [("corners", n_points)]
+    if method == "mixed":
+        n_kmedoid, n_shi_tomasi = n_points // 4, n_points // 3
+        shares = (("kmedoids", n_kmedoid), ("corners", n_shi_tomasi), ("random", n_points - n_kmedoid - n_shi_tomasi))
+        return [(k, n) for k, n in shares if n > 0]
+    raise NotImplementedError(f"Point selection method {method} not implemented")
+
+
+def select_query_points(source, images, query_points_timestep, positive_method: str, positive_points: int,
+                        negative_method: str = None, negative_points: int = 0, stats: dict = None) -> List[torch.Tensor]:
+    """What ``SamPt.extract_query_points`` computes per mask — ``extract_query_points_xy`` of the masks with the positive method,
+    then, with ``negative_points > 0``, of their complements with the negative method, concatenated — from a ``source`` of pixels
+    (``mask_points.HostMasks`` / ``mask_points.DevicePlanes``) that is asked for areas, never for masks: -> M tensors (P+ + P-, 2)
+    float32 (x, y) on the host.  The Shi-Tomasi corners (no RNG) come first, because the size of their k-medoid top-up decides a
+    draw; then every rank of the call is drawn in the selectors' order and goes to the source in ONE ``select``; the k-medoid
+    subsamples are clustered where the source holds them and only the chosen points come back (``take``).  ``stats``: receives the
+    number of draws / repeats / empty masks met (what a test asserts its inputs cover)."""
+    M = source.n_masks
+    groups = [(False, method_shares(positive_method, positive_points))]
+    if negative_points > 0:
+        groups.append((True, method_shares(negative_method, negative_points)))
+    stats = stats if stats is not None else {}
+    for k in ("draw", "repeat", "empty"):
+        stats.setdefault(k, 0)
+    corners = {}
+    for g, (invert, shares) in enumerate(groups):
+        for s, (kind, n) in enumerate(shares):
+            if kind == "corners":
+                for i in range(M):
+                    if source.area(i, invert) > 0:
+                        corners[(g, s, i)] = source.corners(images[int(query_points_timestep[i].item())], i, invert, n)
+    queries, n_queries = [], 0
+    pieces = [[[] for _ in range(M)] for _ in groups]          # per (group, mask): host tensors (x, y) | ("rows", q0, nq) | ("cluster", q0, nq, k)
+
+    def ask(g, i, invert, kind, n, subsample):
+        nonlocal n_queries
+        area = source.area(i, invert)
+        ranks = rank_step(area, n, subsample if kind == "kmedoids" else None)
+        if ranks is None:
+            stats["empty"] += 1
+            print(f"Warning: mask.sum() == 0 in extract_{'kmedoid_points' if kind == 'kmedoids' else 'random_mask_points'}")
+            pieces[g][i].append(torch.zeros((n, 2)))
+            return
+        stats["repeat" if area < n else "draw"] += 1
+        q = np.empty((len(ranks), 3), dtype=np.int32)
+        q[:, 0], q[:, 1], q[:, 2] = i, int(invert), ranks.numpy()
+        queries.append(q)
+        pieces[g][i].append(("cluster", n_queries, len(ranks), n) if kind == "kmedoids" and area >= n else ("rows", n_queries, len(ranks)))
+        n_queries += len(ranks)
+
+    for g, (invert, shares) in enumerate(groups):
+        for s, (kind, n) in enumerate(shares):
+            for i in range(M):
+                if kind != "corners":
+                    ask(g, i, invert, kind, n, 1800)
+                elif source.area(i, invert) == 0:
+                    stats["empty"] += 1
+                    print("Warning: mask.sum() == 0 in extract_corner_points")
+                    pieces[g][i].append(torch.zeros((n, 2)))
+                else:
+                    found = corners[(g, s, i)]
+                    pieces[g][i].append(found)
+                    if len(found) < n:                         # the top-up of extract_corner_points (kmedoid_subsample_size 2000)
+                        ask(g, i, invert, "kmedoids", n - found.shape[0], 2000)
+    yx = source.select(np.concatenate(queries, axis=0)) if n_queries else None
+    rows = []                                                  # rows of yx that are returned, in output order
+    for per_mask in pieces:
+        for plist in per_mask:
+            for p, piece in enumerate(plist):
+                if isinstance(piece, torch.Tensor):
+                    continue
+                q0, nq = piece[1], piece[2]
+                if piece[0] == "cluster":
+                    idx = source.kmedoids(yx[q0:q0 + nq], piece[3])
+                    chosen = [q0 + int(j) for j in idx]
+                else:
+                    chosen = list(range(q0, q0 + nq))
+                plist[p] = ("taken", len(rows), len(chosen))
+                rows += chosen
+    taken = source.take(yx, rows).type(torch.float32).flip(1) if rows else torch.zeros((0, 2))      # (y, x) -> (x, y)
+    out = []
+    for i in range(M):
+        parts = []
+        for per_mask in pieces:
+            parts += [p if isinstance(p, torch.Tensor) else taken[p[1]:p[1] + p[2]] for p in per_mask[i]]
+        out.append(torch.cat(parts, dim=0) if len(parts) != 1 else parts[0])
+    return out
 
 
 def extract_query_points_xy(images, query_masks, query_points_timestep, method: str, points_per_mask: int,

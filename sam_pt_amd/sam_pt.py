@@ -21,7 +21,9 @@ With a predictor that lacks ``encode_frames``/``track_decode`` (e.g. the CPU ora
 
 Also built: ``query_masks`` mode with host-side query-point selection
 (``sam_pt_amd/query_points.py``: random and k-medoids) and point re-initialisation with all four ``reinit_variant``s
-(sam_pt.py:355-543), re-using the cached image embeddings across re-initialisation segments.
+(sam_pt.py:355-543), re-using the cached image embeddings across re-initialisation segments.  With ``SamPt(..., device_reinit=True)``
+the masks that query points are selected from stay on the device as bit-planes: the host sees their areas, decides and draws ranks,
+csrc/mask_points.hip reads the pixels (``SamPt._device_reinit_active`` lists what keeps the host loop).
 Shi-Tomasi / "mixed" point selection restate OpenCV's algorithms on the host (parity unpinned, query_points.py).
 The optional patch-similarity filter (sam_pt.py:597-682, off in every shipped config) is built twice: on the host with a
 restated ``rgb2lab`` (skimage absent: that one function is parity unpinned), which is what runs on CPU tensors, and as one
@@ -79,6 +81,43 @@ def _stack_frames(frames):
     return torch.stack(list(frames), dim=0)
 
 
+def reinit_query_frames(area, target_area, cur_t, start: int, H: int, variant: str):
+    """The frame every tracked object re-initialises from, after a segment that started at frame ``start`` (sam_pt.py:467-505): the
+    rule of the four ``reinit_variant``s as a pure function of mask AREAS, so that the host loop (areas summed from downloaded masks)
+    and ``device_reinit`` (areas from ``sampt_bits_pack``) take the same decision with the same code.  ``area`` float (n_i, frames - 1):
+    the areas on the segment's frames 1 ..; ``target_area`` int (n_i,): the areas on its frame 0; ``cur_t`` int (M,): every object's
+    current query frame; ``H`` the re-initialisation horizon.  -> (q_t int64 (n_i,), indices into frames 1 .., invalid bool (n_i,))."""
+    area = area.clone()
+    area[area <= 25] = torch.nan
+    if H // 4 < area.shape[1]:
+        area[:, :H // 4] = torch.nan
+    n_i = area.shape[0]
+    if variant == "reinit-on-horizon-and-sync-masks":
+        nxt = H - 1 - 1
+        others = cur_t[cur_t > start]
+        if len(others) > 0:
+            nxt = min(nxt, others.min() - start - 1)
+        q_t = torch.full((n_i,), nxt, dtype=torch.int64)
+    elif variant == "reinit-at-median-of-area-diff":
+        q_t = area.nanmedian(dim=1).indices
+    elif variant == "reinit-on-similar-mask-area":
+        diff = torch.abs(area - target_area[:, None])
+        diff[diff.isnan()] = torch.inf
+        q_t = diff.argmin(dim=1)
+    elif variant == "reinit-on-similar-mask-area-and-sync-masks":
+        diff = torch.abs(area - target_area[:, None]) / target_area[:, None]
+        diff[diff.isnan()] = 720
+        per_frame = diff.sum(dim=0)
+        others = cur_t[cur_t > start]
+        if len(others) > 0:
+            per_frame[others.min().item() - start - 1] -= 36
+        q_t = torch.full((n_i,), per_frame.argmin(dim=0), dtype=torch.int64)
+    else:
+        raise ValueError(f"Unknown reinit variant: {variant}")
+    invalid = area[torch.arange(n_i), q_t] <= 0          # NaN area (tiny / empty mask) compares False, as upstream
+    return q_t, invalid
+
+
 class PendingForward:
     """Handle of a clip submitted with ``SamPt.forward_begin``; ``SamPt.forward_end`` turns it into ``forward``'s result."""
 
@@ -103,8 +142,12 @@ class SamPt(nn.Module):
                  iterative_refinement_iterations: int = 12, use_patch_matching_filtering: bool = False,
                  patch_size: int = 3, patch_similarity_threshold: float = 0.01, use_point_reinit: bool = False,
                  reinit_point_tracker_horizon: int = 24, reinit_horizon: int = 24,
-                 reinit_variant: str = "reinit-at-median-of-area-diff", device_tracks: bool = False):
+                 reinit_variant: str = "reinit-at-median-of-area-diff", device_tracks: bool = False, device_reinit: bool = False):
         super().__init__()
+        # device_reinit (not a keyword of the reference; off by default): on the fused path the masks that query points are selected
+        # from — a re-initialisation segment's logits, uploaded query masks — stay on the device as bit-planes; the host sees their
+        # areas and draws ranks, csrc/mask_points.hip turns ranks into pixels — see ``_device_reinit_active`` for when the mode applies
+        self.device_reinit = bool(device_reinit)
         # device_tracks (not a keyword of the reference; off by default): on the fused path the point tracks stay on the device and the
         # prompts are assembled there (sam_pt_amd/prompt_assembly.py) — see ``_device_tracks_active`` for when the mode applies
         self.device_tracks = bool(device_tracks)
@@ -406,8 +449,14 @@ class SamPt(nn.Module):
 
     def extract_query_points(self, images, query_masks, query_points_timestep):
         """Query points (M, P+ + P-, 3) = (t, x, y) from masks: positives from the mask, negatives from its complement
-        (sam_pt.py:238-288).  Host-side selection, see sam_pt_amd/query_points.py."""
+        (sam_pt.py:238-288).  Host-side selection, see sam_pt_amd/query_points.py.  With ``device_reinit`` active and the masks on the
+        HIP device the masks stay there: they are binary by the reference's contract, ``mask != 0`` is packed into bit-planes (so the
+        complement ``1 - mask`` is the clear pixels), the host learns M areas and draws the ranks the host path would draw, the pixels are
+        read on the device (``query_points.select_query_points``): the same points for the same seed."""
         from .query_points import extract_query_points_xy
+        if self._device_reinit_active(images) and query_masks.is_cuda:
+            from .mask_points import planes_of_masks
+            return self._query_points_from_planes(images, planes_of_masks(query_masks), query_points_timestep)
         query_masks = query_masks.cpu()
         query_points_timestep = query_points_timestep.cpu()
         # k-medoid clustering on the device when the frames live there (same points bit for bit; query_points.py)
@@ -419,6 +468,16 @@ class SamPt(nn.Module):
                                           self.negative_point_selection_method, self.negative_points_per_mask, device=dev)
             xy = [torch.cat(x, dim=0) for x in zip(xy, neg)]
         xy = torch.stack(xy, dim=0)
+        t = query_points_timestep[:, None, None].repeat(1, xy.shape[1], 1)
+        return torch.concat([t, xy], dim=2)
+
+    def _query_points_from_planes(self, images, source, query_points_timestep):
+        """``extract_query_points`` from a ``mask_points.DevicePlanes``: (M, P+ + P-, 3) = (t, x, y) on the host."""
+        from .query_points import select_query_points
+        query_points_timestep = query_points_timestep.cpu()
+        xy = torch.stack(select_query_points(source, images, query_points_timestep, self.positive_point_selection_method,
+                                             self.positive_points_per_mask, self.negative_point_selection_method,
+                                             self.negative_points_per_mask), dim=0)
         t = query_points_timestep[:, None, None].repeat(1, xy.shape[1], 1)
         return torch.concat([t, xy], dim=2)
 
@@ -445,7 +504,8 @@ class SamPt(nn.Module):
             scores_per_frame[t:, m], scores_per_frame[:t, m] = sc_r[t:, m], sc_l[:t, m]
         assert not torch.isnan(trajectories).any()
         assert not torch.isnan(logits).any()
-        return trajectories, visibilities, logits, scores_per_frame.nanmean(dim=0), scores_per_frame
+        # (device_tracks with device_reinit: the segments' tracks come home here, once)
+        return trajectories.cpu(), visibilities.cpu(), logits, scores_per_frame.nanmean(dim=0), scores_per_frame
 
     def _forward_w_reinit_inner(self, images, query_points, feats=None):
         n_frames, _, height, width = images.shape
@@ -453,8 +513,11 @@ class SamPt(nn.Module):
         assert self.reinit_point_tracker_horizon >= self.reinit_horizon
         H = self.reinit_horizon
         dev = images.device if feats is not None else torch.device("cpu")
-        trajectories = torch.full((n_frames, n_masks, points_per_mask, 2), torch.nan, dtype=torch.float32)
-        visibilities = torch.full((n_frames, n_masks, points_per_mask), False, dtype=torch.float32)
+        dev_reinit = feats is not None and self._device_reinit_active(images)
+        dev_tracks = feats is not None and self._device_tracks_active(images)        # (segment tracks and their buffers on the device)
+        trk_dev = dev if dev_tracks else torch.device("cpu")
+        trajectories = torch.full((n_frames, n_masks, points_per_mask, 2), torch.nan, dtype=torch.float32, device=trk_dev)
+        visibilities = torch.full((n_frames, n_masks, points_per_mask), False, dtype=torch.float32, device=trk_dev)
         scores_per_frame = torch.full((n_frames, n_masks), torch.nan, dtype=torch.float32)
         logits = torch.full((n_masks, n_frames, height, width), torch.nan, dtype=torch.float32, device=dev)
         current = query_points.clone()
@@ -473,52 +536,19 @@ class SamPt(nn.Module):
                 q_masks_i = self.extract_query_masks(images[start:end_trk], q_i, feats[start:end_trk] if feats is not None else None)
                 assert self.point_tracker_mask_batch_size >= n_masks
                 self.point_tracker.set_masks(q_masks_i)
-            traj_i, vis_i = self._track_points(images[start:end_trk], q_i)
+            traj_i, vis_i = self._track_points(images[start:end_trk], q_i, on_device=dev_tracks)
             traj_i, vis_i = traj_i[:H], vis_i[:H]
             _, logits_i, spf_i = self._apply_sam_to_trajectories(images[start:end], traj_i, vis_i,
                                                                  feats[start:end] if feats is not None else None)
             logits_i = logits_i.type(torch.float32)
             logits[tracked.to(logits.device), start:end] = logits_i
-            pred = (logits_i > 0).cpu()
-            trajectories[start:end, tracked] = traj_i
-            visibilities[start:end, tracked] = vis_i
+            trajectories[start:end, tracked.to(trk_dev)] = traj_i
+            visibilities[start:end, tracked.to(trk_dev)] = vis_i
             scores_per_frame[start:end, tracked] = spf_i
             if end == n_frames:
                 continue
-            # choose the frame to re-initialise from (sam_pt.py:467-505)
-            area = pred[:, 1:, :, :].sum([2, 3]).float()
-            area[area <= 25] = torch.nan
-            if H // 4 < area.shape[1]:
-                area[:, :H // 4] = torch.nan
-            n_i = pred.shape[0]
-            if self.reinit_variant == "reinit-on-horizon-and-sync-masks":
-                nxt = H - 1 - 1
-                others = cur_t[cur_t > start]
-                if len(others) > 0:
-                    nxt = min(nxt, others.min() - start - 1)
-                q_t = torch.full((n_i,), nxt, dtype=torch.int64)
-            elif self.reinit_variant == "reinit-at-median-of-area-diff":
-                q_t = area.nanmedian(dim=1).indices
-            elif self.reinit_variant == "reinit-on-similar-mask-area":
-                target = pred[:, 0, :, :].sum([1, 2])
-                diff = torch.abs(area - target[:, None])
-                diff[diff.isnan()] = torch.inf
-                q_t = diff.argmin(dim=1)
-            elif self.reinit_variant == "reinit-on-similar-mask-area-and-sync-masks":
-                target = pred[:, 0, :, :].sum([1, 2])
-                diff = torch.abs(area - target[:, None]) / target[:, None]
-                diff[diff.isnan()] = 720
-                per_frame = diff.sum(dim=0)
-                others = cur_t[cur_t > start]
-                if len(others) > 0:
-                    per_frame[others.min().item() - start - 1] -= 36
-                q_t = torch.full((n_i,), per_frame.argmin(dim=0), dtype=torch.int64)
-            else:
-                raise ValueError(f"Unknown reinit variant: {self.reinit_variant}")
-            invalid = area[torch.arange(n_i), q_t] <= 0          # NaN area (tiny / empty mask) compares False, as upstream
+            q_t, invalid, upd = self._reinit_step(images[start + 1:end], logits_i, cur_t, start, dev_reinit)
             if (~invalid).sum() > 0:
-                q_masks = pred[:, 1:, :, :][torch.arange(n_i), q_t].type(torch.float32)
-                upd = self.extract_query_points(images[start + 1:end], q_masks[~invalid], q_t[~invalid])
                 valid_tracked = tracked.clone()
                 valid_tracked[tracked] = ~invalid
                 current[valid_tracked] = upd.to(current.device)
@@ -528,10 +558,37 @@ class SamPt(nn.Module):
                 invalid_tracked[tracked] = invalid
                 current[invalid_tracked, :, 0] = n_frames
                 current[invalid_tracked, :, 1:] = 0
-                trajectories[end:, invalid_tracked] = -72
-                visibilities[end:, tracked] = PointVisibilityType.REINIT_FAILED.value
+                trajectories[end:, invalid_tracked.to(trk_dev)] = -72
+                visibilities[end:, tracked.to(trk_dev)] = PointVisibilityType.REINIT_FAILED.value
                 logits[invalid_tracked.to(logits.device), end:] = -float("inf")
         return trajectories, visibilities, logits, scores_per_frame.nanmean(dim=1), scores_per_frame
+
+    def _reinit_step(self, images_after, logits_i, cur_t, start, dev_reinit):
+        """One segment's re-initialisation decision and its new query points (sam_pt.py:467-533).  ``logits_i`` f32 (n_i, frames, H, W)
+        of the tracked objects on the segment that started at ``start``; ``images_after``: the segment's frames 1 ..  -> (q_t (n_i,):
+        the frame, among those, every object re-initialises from; invalid bool (n_i,); the valid objects' query points (n_valid, P, 3) =
+        (t, x, y) with t = q_t, or None when there is none).  Host loop: the masks ``logits_i > 0`` are downloaded, summed and read
+        with ``nonzero()``.  ``dev_reinit``: they are packed into bit-planes on the device (the same predicate, NaN clear), the host
+        sees n_i x frames areas, and frame 1 + q_t of object j is plane j * frames + 1 + q_t[j]."""
+        H = self.reinit_horizon
+        if dev_reinit:
+            from .mask_points import DevicePlanes, device_reinit_areas
+            bits, counts = device_reinit_areas(logits_i)
+            area, target_area = counts[:, 1:].float(), counts[:, 0]
+        else:
+            pred = (logits_i > 0).cpu()
+            area, target_area = pred[:, 1:, :, :].sum([2, 3]).float(), pred[:, 0, :, :].sum([1, 2])
+        n_i = area.shape[0]
+        q_t, invalid = reinit_query_frames(area, target_area, cur_t, start, H, self.reinit_variant)
+        upd = None
+        if (~invalid).sum() > 0 and dev_reinit:
+            chosen = (torch.arange(n_i) * counts.shape[1] + 1 + q_t)[~invalid]
+            source = DevicePlanes(bits.index_select(0, chosen.to(bits.device)), counts.reshape(-1)[chosen].tolist(), logits_i.shape[-2])
+            upd = self._query_points_from_planes(images_after, source, q_t[~invalid])
+        elif (~invalid).sum() > 0:
+            q_masks = pred[:, 1:, :, :][torch.arange(n_i), q_t].type(torch.float32)
+            upd = self.extract_query_points(images_after, q_masks[~invalid], q_t[~invalid])
+        return q_t, invalid, upd
 
     @staticmethod
     def _resize_logits(logits, target_hw):
@@ -568,16 +625,31 @@ class SamPt(nn.Module):
     def _device_tracks_active(self, images, frame_ids=None) -> bool:
         """Whether this clip runs with ``device_tracks``: tracker results left on the device (``results_on_device``), border rule
         and prompt assembly there (sam_pt_amd/prompt_assembly.py), one download of 2 * T * M counts in place of the trajectories'.
-        Everything else takes the host path, silently: ``use_point_reinit`` (the re-initialisation loop reads masks and tracks on
-        the host), a tracker with ``set_masks`` (SuperGlue: runs after the encoder, on host-side masks) or without
+        Everything else takes the host path, silently: ``use_point_reinit`` without an active ``device_reinit`` (the host's
+        re-initialisation loop reads masks and tracks there; with ``_device_reinit_active`` every segment's tracks stay on the device,
+        its prompts are assembled there and the per-segment buffers come home once at the end), a tracker with ``set_masks``
+        (SuperGlue: runs after the encoder, on host-side masks) or without
         ``results_on_device`` (not an engine tracker), ``max_other_objects_positive_points`` (its ``np.random.choice`` is host RNG),
         a predictor without ``encode_frames`` / ``track_decode``, frames that are not on a HIP device, and ``video["frame_ids"]``
         (frame sharding selects the SAM stage's frames from the whole clip's tracks on the host)."""
         pred = self.sam_predictor
         return bool(self.device_tracks and hasattr(pred, "encode_frames") and hasattr(pred, "track_decode")
-                    and not self.use_point_reinit and not hasattr(self.point_tracker, "set_masks")
+                    and (not self.use_point_reinit or self._device_reinit_active(images))
+                    and not hasattr(self.point_tracker, "set_masks")
                     and hasattr(self.point_tracker, "results_on_device") and self.max_other_objects_positive_points is None
                     and frame_ids is None and bool(getattr(images, "is_cuda", False)))
+
+    def _device_reinit_active(self, images) -> bool:
+        """Whether this clip runs with ``device_reinit``: the masks that query points are selected from — every re-initialisation
+        segment's logits, and query masks handed over as HIP tensors — are packed into bit-planes where they lie (``sampt_bits_pack``),
+        the host downloads their areas, takes the re-initialisation decision (``reinit_query_frames``) and draws ranks from them, and
+        ``sampt_bits_select`` reads the pixels (sam_pt_amd/mask_points.py, ``query_points.select_query_points``): the same points, the
+        same generator state.  Everything else takes the host loop, silently: a predictor without ``encode_frames`` / ``track_decode``
+        (no fused path, no cached embeddings), frames that are not on a HIP device, and a tracker with ``set_masks`` (SuperGlue consumes
+        host-side query masks per window)."""
+        pred = self.sam_predictor
+        return bool(self.device_reinit and hasattr(pred, "encode_frames") and hasattr(pred, "track_decode")
+                    and not hasattr(self.point_tracker, "set_masks") and bool(getattr(images, "is_cuda", False)))
 
     def _track_points(self, rgbs, query_points, on_device=False):
         """Chunks of ``point_tracker_mask_batch_size`` objects per tracker call (sam_pt.py:545-576, 578-692).  ``on_device``
