@@ -391,8 +391,11 @@ int sampt_conv_set_halo(int on);
  *   scatter = 0: dst[r] = src[idx[r] / n_objects]                                   (item r's frame embedding into the chain's input)
  *   scatter = 1: dst[(idx[r] % n_objects) * n_frames + idx[r] / n_objects] = src[r]  (masks into logits [n_objects][n_frames][H * W];
  *                scores with n_objects = 1: dst[idx[r]] = src[r])
- * row_bytes: a multiple of 16 with 16-byte aligned buffers, or 4.  sampt_fill_f32: dst[0 .. n) = value (the -inf of items without
- * a prompt, sam_pt.py:766-767). */
+ * row_bytes: any positive multiple of 4, src and dst 4-byte aligned (frames of every size: H * W floats).  Rows that are a multiple
+ * of 16 bytes on 16-byte aligned src and dst move in 16-byte units, all others word by word.  A row_bytes that is no multiple of 4, a
+ * pointer off 4-byte alignment, a null pointer, or rows, n_objects (n_frames of a scatter) <= 0: SAMPT_ERR_ARG with the argument
+ * named in sampt_last_error, nothing launched.  sampt_fill_f32: dst[0 .. n) = value, dst 4-byte aligned, n > 0 (the -inf of items
+ * without a prompt, sam_pt.py:766-767). */
 int sampt_move_rows(const void* src, void* dst, const int* idx, int rows, size_t row_bytes, int n_objects, int n_frames, int scatter,
                     sampt_stream_t stream);
 int sampt_fill_f32(float* dst, size_t n, float value, sampt_stream_t stream);

@@ -1592,10 +1592,20 @@ int sampt_sam_mask_dot(const float* up, const float* hyper, int ld_hyper, float*
 
 int sampt_move_rows(const void* src, void* dst, const int* idx, int rows, size_t row_bytes, int n_objects, int n_frames, int scatter,
                     sampt_stream_t stream) {
+  if (!src || !dst || !idx) return fail(SAMPT_ERR_ARG, "sampt_move_rows: src, dst or idx is null");
+  if (rows <= 0 || n_objects <= 0 || (scatter && n_frames <= 0))
+    return fail(SAMPT_ERR_ARG, "sampt_move_rows: rows, n_objects (and n_frames of a scatter) must be positive");
+  if (row_bytes == 0 || (row_bytes & 3) || (long)row_bytes <= 0)
+    return fail(SAMPT_ERR_ARG, "sampt_move_rows: row_bytes = " + std::to_string(row_bytes) + " is not a positive multiple of 4");
+  if (((uintptr_t)src | (uintptr_t)dst | (uintptr_t)idx) & 3) return fail(SAMPT_ERR_ARG, "sampt_move_rows: src, dst and idx must be 4-byte aligned");
   return move_rows(src, dst, idx, rows, (long)row_bytes, n_objects, n_frames, scatter, (hipStream_t)stream);
 }
 
-int sampt_fill_f32(float* dst, size_t n, float value, sampt_stream_t stream) { return fill_f32(dst, (long)n, value, (hipStream_t)stream); }
+int sampt_fill_f32(float* dst, size_t n, float value, sampt_stream_t stream) {
+  if (!dst || ((uintptr_t)dst & 3)) return fail(SAMPT_ERR_ARG, "sampt_fill_f32: dst must be non-null and 4-byte aligned");
+  if (n == 0 || (long)n <= 0) return fail(SAMPT_ERR_ARG, "sampt_fill_f32: n must be positive");
+  return fill_f32(dst, (long)n, value, (hipStream_t)stream);
+}
 
 int sampt_conv_stem7x7(const float* x_nhwc4, const float* w, const float* bias, float* y, int n, int H, int W, float eps,
                        float* mean_rstd, void* ws, size_t ws_bytes, sampt_stream_t stream) {

@@ -38,7 +38,8 @@ int rgb_u8chw_to_nhwc4(const void* src, int src_f32, float* dst, int T, int H, i
 // hipGraph reads and writes fixed buffers, so a chunk's embeddings are gathered into them and its masks / scores scattered out):
 //   gather : dst[r] = src[idx[r] / nm]                       (the embedding of item r's frame)
 //   scatter: dst[(idx[r] % nm) * nf + idx[r] / nm] = src[r]   (logits [nm][nf][H*W]; scores: nm = 1 -> dst[idx[r]])
-// rows of row16 16-byte units; one workgroup walks a row segment of 256 units
+// rows of row16 16-byte units; one workgroup walks a row segment of 256 units.  Rows that are not made of aligned 16-byte units (a
+// frame whose area is no multiple of 4, the 4-byte scores, a buffer off 16-byte alignment) move word by word: k_move_words
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_move_rows(const float4* __restrict__ src, float4* __restrict__ dst, const int* __restrict__ idx,
                                                    long row16, int nm, int nf, int scatter) {
@@ -49,27 +50,32 @@ __global__ __launch_bounds__(256) void k_move_rows(const float4* __restrict__ sr
   dst[dr * row16 + u] = src[sr * row16 + u];
 }
 
-__global__ void k_move_words(const float* __restrict__ src, float* __restrict__ dst, const int* __restrict__ idx, int rows, int nm,
-                             int nf, int scatter) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= rows) return;
+// rows of `words` 4-byte words on 4-byte aligned buffers: one thread per word, consecutive threads walk a row (words == 1, the
+// scores: one thread per row)
+__global__ __launch_bounds__(256) void k_move_words(const float* __restrict__ src, float* __restrict__ dst, const int* __restrict__ idx,
+                                                    long total, long words, int nm, int nf, int scatter) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const long r = i / words, w = i - r * words;
   const int it = idx[r];
-  if (scatter) dst[(long)(it % nm) * nf + it / nm] = src[r];
-  else dst[r] = src[it / nm];
+  const long sr = scatter ? r : it / nm, dr = scatter ? (long)(it % nm) * nf + it / nm : r;
+  dst[dr * words + w] = src[sr * words + w];
 }
 
-static int move_words(const void* src, void* dst, const int* idx, int rows, int nm, int nf, int scatter, hipStream_t s) {
-  hipLaunchKernelGGL(k_move_words, dim3(cdiv(rows, 256)), dim3(256), 0, s, (const float*)src, (float*)dst, idx, rows, nm, nf, scatter);
+static int move_words(const void* src, void* dst, const int* idx, int rows, long words, int nm, int nf, int scatter, hipStream_t s) {
+  const long total = (long)rows * words, blocks = (total + 255) / 256;
+  if (blocks > 0x7fffffffL) return SAMPT_ERR_UNSUPPORTED;      // (2^39 words: no clip is that large)
+  hipLaunchKernelGGL(k_move_words, dim3((unsigned)blocks), dim3(256), 0, s, (const float*)src, (float*)dst, idx, total, words, nm, nf,
+                     scatter);
   SAMPT_CHECK_LAUNCH("move_words");
   return SAMPT_OK;
 }
 
 int move_rows(const void* src, void* dst, const int* idx, int rows, long row_bytes, int nm, int nf, int scatter, hipStream_t s) {
-  if (!src || !dst || !idx || rows <= 0 || row_bytes <= 0 || nm <= 0) return SAMPT_ERR_ARG;
-  if ((row_bytes & 15) || (((uintptr_t)src | (uintptr_t)dst) & 15)) {      // short rows (scores: 4 bytes): one thread per row
-    if (row_bytes != 4) return SAMPT_ERR_UNSUPPORTED;
-    return move_words(src, dst, idx, rows, nm, nf, scatter, s);
-  }
+  if (!src || !dst || !idx || rows <= 0 || row_bytes <= 0 || nm <= 0 || (scatter && nf <= 0)) return SAMPT_ERR_ARG;
+  if ((row_bytes & 3) || (((uintptr_t)src | (uintptr_t)dst | (uintptr_t)idx) & 3)) return SAMPT_ERR_ARG;
+  if ((row_bytes & 15) || (((uintptr_t)src | (uintptr_t)dst) & 15))        // no aligned 16-byte units: word by word
+    return move_words(src, dst, idx, rows, row_bytes / 4, nm, nf, scatter, s);
   const long row16 = row_bytes / 16;
   hipLaunchKernelGGL(k_move_rows, dim3((unsigned)cdiv(row16, 256), rows), dim3(256), 0, s, (const float4*)src, (float4*)dst, idx, row16,
                      nm, nf, scatter);

@@ -27,12 +27,12 @@ def clip():
 
 
 # ---------------------------------------------------------------------------------------------- step level
-def _segment_logits():
-    """f32 logits of 3 objects x 6 frames of 128 x 256: discs of varying radius; blobs of at most 25 pixels, some of fewer pixels than
-    points are asked for; an object that is empty from frame 2 on."""
+def _segment_logits(H=128, W=256):
+    """f32 logits of 3 objects x 6 frames of H x W (at least 121 x 215, which holds every shape below): discs of varying radius; blobs
+    of at most 25 pixels, some of fewer pixels than points are asked for; an object that is empty from frame 2 on."""
     g = torch.Generator().manual_seed(3)
-    yy, xx = torch.meshgrid(torch.arange(128), torch.arange(256), indexing="ij")
-    masks = torch.zeros(3, 6, 128, 256, dtype=torch.bool)
+    yy, xx = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
+    masks = torch.zeros(3, 6, H, W, dtype=torch.bool)
     for f, r in enumerate([14, 9, 17, 12, 21, 11]):
         masks[0, f] = ((yy - 60 - f) ** 2 + (xx - 90 - 4 * f) ** 2) <= r * r
     for f, npx in enumerate([25, 2, 25, 9, 2, 3]):

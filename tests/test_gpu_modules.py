@@ -829,18 +829,20 @@ def test_set_image_with_resize_vs_pil_and_oracle(dev):
     assert m1.shape == (1, 72, 128) and np.abs(m1 - m0[0].numpy()).max() < 3e-4 and np.abs(i1 - i0[0].numpy()).max() < 1e-4
 
 
-def test_arbitrary_frame_sizes(dev, pips_sd):
+@pytest.mark.parametrize("H,W", [(120, 214), (121, 215), (215, 121)])
+def test_arbitrary_frame_sizes(dev, pips_sd, H, W):
     """Frames whose sides are not multiples of 32 and whose longest side is not the SAM input size (e.g. native 480 x 854):
     the tracker runs at frame resolution (floor-divided feature maps / pyramid like the reference), SAM resizes with the
     PIL-exact kernel, masks come back at frame resolution.  Tracker vs oracle; fused device path vs the call-by-call
-    protocol; the latter vs the oracle predictor driven the same way."""
+    protocol; the latter vs the oracle predictor driven the same way.  121 x 215 and its portrait twin have an area that is no
+    multiple of 4: the fused path's staging then moves rows that are not made of 16-byte units."""
     from oracle import pips_ref as O
     from oracle import sam_ref as R
     from sam_pt_amd.point_tracker import PipsPointTracker
     from sam_pt_amd.sam_predictor import SamHip, SamPredictor
     from sam_pt_amd.sam_pt import SamPt
     from sam_pt_amd.weights import SAM_CONFIGS, init_sam_state_dict
-    frames, centres = synthetic_clip(T=9, H=120, W=214, seed=21)
+    frames, centres = synthetic_clip(T=9, H=H, W=W, seed=21)
     q = disc_queries(centres, n_pos=4, r=8.0)[None]
     tr_ref, vi_ref = O.PipsTrackerRef(pips_sd).forward(frames[None], q)
     trk = PipsPointTracker(state_dict=pips_sd)
@@ -851,9 +853,9 @@ def test_arbitrary_frame_sizes(dev, pips_sd):
     pred = SamPredictor(SamHip(config=cfg, state_dict=sd, precision="f32").to(dev))
     kw = dict(sam_iou_threshold=-1e9, positive_points_per_mask=4, negative_points_per_mask=0, iterative_refinement_iterations=2)
     model = SamPt(trk, pred, **kw).eval()
-    video = {"image": [f for f in frames], "target_hw": (120, 214), "query_points": q}
+    video = {"image": [f for f in frames], "target_hw": (H, W), "query_points": q}
     out = model(video)
-    assert out["logits"][0].shape == (9, 120, 214)
+    assert out["logits"][0].shape == (9, H, W)
     images = frames.to(dev)
     _, l_s, s_s = model._apply_sam_to_trajectories(images, out["trajectories"].cpu(), out["visibilities"].cpu(), None)
     l_f = torch.stack(out["logits"]).cpu()
