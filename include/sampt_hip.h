@@ -896,6 +896,20 @@ int sampt_gemm_f32_route(int M, int N, int K, int lda, int ldc, int invariant, i
 int sampt_gemm_ex(int dtype, const void* A_dev, const void* W_dev, const float* bias_dev, const float* res_dev,
                   void* C_dev, int M, int N, int K, int act, float alpha, const int32_t* rowmap_dev,
                   const int32_t* a_rowmap_dev, int res_mod, int ldr, sampt_stream_t stream);
+/* sampt_gemm_ex for dtype 1 .. 4 on the persistent 256 x 256 fp16 kernel (csrc/gemm_f16_p8.hip) and on no other: a shape or an
+ * alignment that kernel does not take (M < 256, N % 256, stored K % 128, operands not 16-byte aligned, an x3 product with fp16
+ * output, ...) returns SAMPT_ERR_UNSUPPORTED and nothing is computed.  heads, hd, rows: the head-major destination of
+ * sampt_gemm_f16_head_major (dtype 2; all 0 = off).  wgs_per_xcd: persistent workgroups per XCD for this call, 0 = one per CU (32);
+ * stagger: phase groups for this call, 0 = the process setting (sampt_gemm_set_stagger), 1 = off.  Reads sampt_gemm_set_trim /
+ * _schedule / _stagger like every launch of the kernel and writes no process-wide state.  Whatever the workgroup count, the trim
+ * rule, the schedule and the phase groups, the bits of C are the same.
+ * sampt_gemm_f16_p8_plan (host only): what the launcher of that kernel does with an M x N product (M >= 256, N % 256 == 0) allowed
+ * wgs_per_xcd workgroups per XCD (0 = 32) — the workgroups per XCD it launches (8 XCDs), the tile rounds (the longest tile list of a
+ * workgroup) and the strip height in 256-row panels of the tile order.  trim: 0 / 1, -1 = the process setting (sampt_gemm_set_trim). */
+int sampt_gemm_f16_p8(int dtype, const void* A_dev, const void* W_dev, const float* bias_dev, const float* res_dev, void* C_dev,
+                      int M, int N, int K, int act, float alpha, const int32_t* rowmap_dev, const int32_t* a_rowmap_dev,
+                      int res_mod, int ldr, int heads, int hd, int rows, int wgs_per_xcd, int stagger, sampt_stream_t stream);
+int sampt_gemm_f16_p8_plan(int M, int N, int wgs_per_xcd, int trim, int* workgroups_per_xcd, int* rounds, int* strip_rows);
 /* dtype 3 / 4 of sampt_gemm_ex: fp32-grade product on the fp16 matrix pipe.  A [M][2K] and W [N][2K] are "x3 rows": every
  * block of 32 consecutive k of a logical row is stored as 64 halves hi(32) | lo(32), v = hi + lo with hi = fp16(v),
  * lo = fp16(v - hi) (sampt_split_rows_x3; weights are split after scaling by 2^8 — sam_pt_amd/pack.py:x3_rows — and the

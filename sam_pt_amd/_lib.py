@@ -230,6 +230,9 @@ _SIGS = {
     "sampt_pips_mix_mlp_x3": (c_int, [_P, _P, _P, _P, c_int, c_int, _P]),
     "sampt_pips_mix_reduce_f32": (c_int, [_P, c_int, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "sampt_gemm_ex": (c_int, [c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, c_int, c_int, _P]),
+    "sampt_gemm_f16_p8": (c_int, [c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, c_int, c_int, c_int, c_int, c_int,
+                                  c_int, c_int, _P]),
+    "sampt_gemm_f16_p8_plan": (c_int, [c_int, c_int, c_int, c_int, C.POINTER(c_int), C.POINTER(c_int), C.POINTER(c_int)]),
     "sampt_conv2d_nhwc": (c_int, [c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "sampt_instance_norm_nhwc": (c_int, [_P, c_int, c_int, c_int, c_float, c_int, _P, _P, c_size_t, _P]),
     "sampt_instance_norm_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),

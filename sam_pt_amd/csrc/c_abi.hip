@@ -1491,6 +1491,39 @@ int sampt_gemm_ex(int dtype, const void* A, const void* W, const float* bias, co
   return dtype == 0 ? gemm_f32(p, (hipStream_t)stream) : gemm_f16(p, (hipStream_t)stream);
 }
 
+int sampt_gemm_f16_p8(int dtype, const void* A, const void* W, const float* bias, const float* res, void* C, int M, int N, int K,
+                      int act, float alpha, const int32_t* rowmap, const int32_t* a_rowmap, int res_mod, int ldr, int heads, int hd,
+                      int rows, int wgs_per_xcd, int stagger, sampt_stream_t stream) {
+  const bool hm = heads != 0 || hd != 0 || rows != 0;
+  if (dtype < 1 || dtype > 4 || !A || !W || !C || M <= 0 || N <= 0 || K <= 0 || res_mod < 0 || ldr < 0 || wgs_per_xcd < 0 ||
+      wgs_per_xcd > 32 || stagger < 0 || stagger > 8)
+    return fail(SAMPT_ERR_ARG, "sampt_gemm_f16_p8: dtype 1 .. 4, non-null operands, wgs_per_xcd 0 .. 32, stagger 0 .. 8");
+  if (hm && (heads <= 0 || hd < 4 || hd % 4 || N % (heads * hd) || rows < (rowmap ? 1 : M)))
+    return fail(SAMPT_ERR_ARG, "sampt_gemm_f16_p8: head-major needs hd % 4 == 0, N % (heads * hd) == 0, rows >= M without a rowmap");
+  GemmP p = gemm_linear(A, K, W, bias, C, N, M, N, K, act, res, ldr > 0 ? ldr : N, res_mod);
+  p.alpha = alpha, p.rowmap = rowmap, p.a_rowmap = a_rowmap, p.out_f16 = dtype == 2;
+  if (dtype == 3 || dtype == 4) {
+    p.x3 = 1, p.K = 2 * K, p.lda = 2 * K, p.ldw = 2 * K;
+    if (dtype == 4) p.out_f16 = 2, p.ldc = 2 * N;
+  }
+  if (hm) {                          // a plain fp16 destination; the kernel has none for an x3 product and refuses it
+    p.hm_heads = heads, p.hm_hd = hd, p.hm_rows = rows;
+    if (dtype >= 2) p.out_f16 = 1, p.ldc = N;
+  }
+  p.p8_wgs = wgs_per_xcd, p.p8_stagger = stagger;
+  // the epilogue's 16-byte accesses (the launcher checks A and W)
+  if ((((uintptr_t)bias | (uintptr_t)res) & 15) || ((uintptr_t)C & (p.out_f16 ? 7 : 15))) return SAMPT_ERR_UNSUPPORTED;
+  return gemm_f16_p8_launch(p, (hipStream_t)stream);
+}
+
+int sampt_gemm_f16_p8_plan(int M, int N, int wgs_per_xcd, int trim, int* workgroups_per_xcd, int* rounds, int* strip_rows) {
+  if (M < 256 || N < 256 || N % 256 || wgs_per_xcd < 0 || wgs_per_xcd > 32 || trim < -1 || trim > 1 || !workgroups_per_xcd || !rounds ||
+      !strip_rows)
+    return fail(SAMPT_ERR_ARG, "sampt_gemm_f16_p8_plan: M >= 256, N a multiple of 256, wgs_per_xcd 0 .. 32, trim -1 / 0 / 1");
+  gemm_f16_p8_plan(M, N, wgs_per_xcd, trim < 0 ? sampt::g_p8_trim : trim, workgroups_per_xcd, rounds, strip_rows);
+  return SAMPT_OK;
+}
+
 int sampt_kmedoids_rowsums_f64(const float* xy, int n, double* out, sampt_stream_t stream) {
   int rc = kmedoids_rowsums(xy, n, out, (hipStream_t)stream);
   return rc == SAMPT_ERR_ARG ? fail(rc, "sampt_kmedoids_rowsums_f64: bad arguments (1 <= n <= 2048)") : rc;

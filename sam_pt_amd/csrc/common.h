@@ -242,6 +242,10 @@ extern int g_p8_trim;
 extern int g_thin_min_wgs; // gemm.hip: workgroups a thin f32 GEMM must keep when it grows its tile (sampt_gemm_set_thin_min_wgs)
 int gemm_f32(const GemmP& p, hipStream_t s);
 int gemm_f16(const GemmP& p, hipStream_t s);
+// gemm_f16_p8.hip: the persistent 256 x 256 fp16 kernel alone — SAMPT_ERR_UNSUPPORTED for a shape it does not take (gemm_f16 then
+// goes on to the other kernels) — and the launch plan it follows (host only): workgroups per XCD, tile rounds, strip height
+int gemm_f16_p8_launch(const GemmP& p, hipStream_t s);
+void gemm_f16_p8_plan(int M, int N, int wgs_allowed, int trim, int* workgroups_per_xcd, int* rounds, int* strip_rows);
 // the split-K factor gemm_f32 will choose for this problem (1 = no split; needs p.splitk_ws / splitk_ws_floats set)
 int gemm_f32_plan_splitk(const GemmP& p);
 // the kernel gemm_f32 will launch for this problem and the number of K partitions whose partial sums it adds at the end (lanes of a

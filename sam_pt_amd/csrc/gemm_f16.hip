@@ -218,8 +218,6 @@ __global__ __launch_bounds__((BM / WTM) * (BN / WTN) * 64, 4) void gemm_f16_glds
   }
 }
 
-int gemm_f16_p8_launch(const GemmP& p, hipStream_t s);   // gemm_f16_p8.hip
-
 // returns SAMPT_ERR_UNSUPPORTED when the shape does not fit this kernel (caller falls back to gemm_kernel)
 int gemm_f16_glds_launch(const GemmP& p, hipStream_t s) {
   {

@@ -361,6 +361,32 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_p8(GemmP p) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the dummy tail stages must land before the LDS is handed on
 }
 
+// The launch plan of an M x N product: what gemm_f16_p8_launch launches and what sampt_gemm_f16_p8_plan reports.  wgs: allowed
+// workgroups per XCD (GemmP::p8_wgs; outside 1 .. 32: one per CU = 32), trim: sampt_gemm_set_trim's rule on / off.  rounds = the
+// longest tile list of any workgroup.  Host only.
+void gemm_f16_p8_plan(int M, int N, int wgs_allowed, int trim, int* workgroups_per_xcd, int* rounds_out, int* strip_rows) {
+  const int nt_m = cdiv(M, 256), nt_n = N / 256;
+  int R = 4;                      // strip height in row panels (2 / 8 measured: more L2 misses, profiles/r3_gemm_hbm_traffic_strip*)
+  if (R > nt_m) R = nt_m;
+  const long ntiles = (long)nt_m * nt_n;
+  // workgroups per XCD: one per CU (32) by default; fewer leaves whole CUs to kernels of other streams (a 512-thread,
+  // 128-KiB workgroup owns its CU: nothing else becomes resident beside it)
+  const int wgs = wgs_allowed >= 1 && wgs_allowed <= 32 ? wgs_allowed : 32;
+  int per_xcd = (int)((ntiles + 7) / 8), rounds = 1;
+  if (per_xcd > wgs) {
+    // An XCD's tiles take ceil(tiles / workgroups) rounds whatever the remainder: the smallest workgroup count with the SAME number
+    // of rounds finishes at the same time and leaves the other CUs to whoever runs beside the launch (ViT-H, 8 frames: proj / fc2
+    // have 80 tiles per XCD = 3 rounds on 30 workgroups and on 27; the tracker's window chain then ends 15 ms earlier beside an
+    // unchanged encoder, profiles/r6_c22_*).  Same tiles, same results.
+    const int tpx = per_xcd;
+    rounds = cdiv(tpx, wgs);
+    per_xcd = wgs;
+    if (trim)
+      while (per_xcd > 1 && cdiv(tpx, per_xcd - 1) == rounds) --per_xcd;
+  }
+  *workgroups_per_xcd = per_xcd, *rounds_out = rounds, *strip_rows = R;
+}
+
 // returns SAMPT_ERR_UNSUPPORTED when the shape does not fit this kernel
 int gemm_f16_p8_launch(const GemmP& p, hipStream_t s) {
   if (p.conv || p.w_kn || p.nb1 * p.nb2 != 1 || (p.K % 128) || p.M < 256 || (p.N % 256)) return SAMPT_ERR_UNSUPPORTED;
@@ -373,26 +399,10 @@ int gemm_f16_p8_launch(const GemmP& p, hipStream_t s) {
   if ((double)p.M * p.lda * 2.0 >= 4294967296.0 || (double)p.N * p.ldw * 2.0 >= 4294967296.0) return SAMPT_ERR_UNSUPPORTED;
   if (p.act != ACT_NONE && p.act != ACT_GELU) return SAMPT_ERR_UNSUPPORTED;
   GemmP q = p;
-  const int nt_m = cdiv(p.M, 256), nt_n = p.N / 256;
-  int R = 4;                      // strip height in row panels (2 / 8 measured: more L2 misses, profiles/r3_gemm_hbm_traffic_strip*)
-  if (R > nt_m) R = nt_m;
+  int per_xcd, rounds, R;
+  gemm_f16_p8_plan(p.M, p.N, p.p8_wgs, g_p8_trim, &per_xcd, &rounds, &R);
   q.xcd_swizzle = R;
   if (q.p8_stagger == 0) q.p8_stagger = g_p8_stagger;
-  const long ntiles = (long)nt_m * nt_n;
-  // workgroups per XCD: one per CU (32) by default; fewer leaves whole CUs to kernels of other streams (a 512-thread,
-  // 128-KiB workgroup owns its CU: nothing else becomes resident beside it)
-  const int wgs = p.p8_wgs >= 1 && p.p8_wgs <= 32 ? p.p8_wgs : 32;
-  int per_xcd = (int)((ntiles + 7) / 8);
-  if (per_xcd > wgs) {
-    // An XCD's tiles take ceil(tiles / workgroups) rounds whatever the remainder: the smallest workgroup count with the SAME number
-    // of rounds finishes at the same time and leaves the other CUs to whoever runs beside the launch (ViT-H, 8 frames: proj / fc2
-    // have 80 tiles per XCD = 3 rounds on 30 workgroups and on 27; the tracker's window chain then ends 15 ms earlier beside an
-    // unchanged encoder, profiles/r6_c22_*).  Same tiles, same results.
-    const int tpx = per_xcd, rounds = cdiv(tpx, wgs);
-    per_xcd = wgs;
-    if (g_p8_trim)
-      while (per_xcd > 1 && cdiv(tpx, per_xcd - 1) == rounds) --per_xcd;
-  }
   const dim3 grid(8 * per_xcd), block(512);
 #define P8_LAUNCH(AC, OU, X)                                                                \
   do {                                                                                      \
